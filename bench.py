@@ -11,10 +11,17 @@ such a call as two concurrent 28-frame lanes -- with the connector + gate pass o
 (identical results; `--batch 28 --no-pipeline` is the plain one-lane schedule of round 1, also printed as a leg of every run).
 Frames are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel = the tiled MFMA GEMM; HIP events recorded on the
-launch stream: inside the timed region for the one-lane schedule, on one-lane plain steps right after it when the timed steps run
-two kernels at a time -- `roofline.measured_on`) and `cpu_baseline` (the oracle -- a plain-torch CPU port of the reference
-arithmetic -- timed on this host on a bounded sample; rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up (weights, frames, the untimed schedule
+pick), warm-up, the timed steps, `--dump-outputs`, the line.  `--full` adds every other leg, each outside the timed region: `roofline`
+(dominant kernel = the tiled MFMA GEMM; HIP events recorded on the launch stream: inside the timed region for the one-lane schedule,
+on one-lane plain steps right after it when the timed steps run two kernels at a time -- `roofline.measured_on`), `cpu_baseline` (the
+oracle -- a plain-torch CPU port of the reference arithmetic -- timed on this host on a bounded sample; rank 0, N=1 only), the
+Mistral-7B decode / prefill / end-to-end legs, the other precisions and schedules (the `--no-*` switches trim `--full`).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32): `gate_logits` [frames of the
+step, 2], `gate_decisions` [frames of the step], and the step's rows of the stream's token store, `frame_tokens` [frames of the step,
+d_model].  Frames, weights and the walk over the stream are seeded and do not depend on the schedule picked, so two builds run with
+the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -780,6 +787,23 @@ def synthetic_frames_gpu(n: int, size: int, seed: int, rank: int) -> torch.Tenso
     return out
 
 
+def dump_outputs(path: str, outs, tokens, cap_bytes: int = 48 << 20) -> None:
+    """--dump-outputs: the last timed step as its caller received it -- `outs` = the (gate logits [n, 2], decisions [n]) of every call of
+    the step, in call order -- plus the step's rows of the token store, as float32 .npy files under `path`.  A token block above
+    `cap_bytes` is cut to a fixed, seeded choice of rows (sorted; the same rows for the same step size), `frame_tokens_rows` names them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "gate_logits.npy"), torch.cat([o[0] for o in outs]).float().cpu().numpy())
+    np.save(os.path.join(path, "gate_decisions.npy"), torch.cat([o[1] for o in outs]).float().cpu().numpy())
+    tok = tokens.float().cpu().numpy()
+    keep = cap_bytes // (tok.shape[1] * 4)
+    if tok.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(1234).choice(tok.shape[0], size=keep, replace=False))
+        np.save(os.path.join(path, "frame_tokens_rows.npy"), rows.astype(np.float64))
+        tok = tok[rows]
+    np.save(os.path.join(path, "frame_tokens.npy"), tok)
+
+
 def usable_cores() -> int:
     """threads the process may actually run: min(affinity, cgroup cpu.max quota)."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -1046,7 +1070,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32, help="timed steps.  The timed region is always about ONE pass over the 1800-frame (60 s x 30 fps) "
-                    "stream of BASELINE configs[1]: a step is round(1800 / (steps x batch)) >= 1 calls of `--batch` frames (32 steps x 56 frames: one call)")
+                    "stream of BASELINE configs[1]: a step is round(1800 / (steps x batch)) >= 1 calls of `--batch` frames (32 steps x 56 frames: one call); "
+                    "when the batch is picked here a step is that many units of 56 frames, as one call of 56 or two of 28 each")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="frames per call.  > 28: the tower runs as two concurrent half batches (two lanes, "
                                                           "sm_vit_encode); a 28-frame lane is 28 x 577 tokens = 63.1 tiles of 256 rows, so every ViT "
@@ -1066,7 +1091,13 @@ def main():
     ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary legs (teacher-forced eval, ingest front-end, per-call latency)")
     ap.add_argument("--stream-frames", type=int, default=1800, help="frames of the synthetic stream (default: the 60 s x 30 fps of BASELINE configs[1]).  Only for "
                     "rocprofv3 COUNTER passes, which intercept every dispatch: generating 1800 frames is ~25 000 small launches and crashed the profiler")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (roofline segments, CPU baseline, decode / prefill / end-to-end, "
+                    "other precisions and schedules, calibration); without it the run is set-up, warm-up, the timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the last step's outputs (gate logits, decisions, frame tokens) "
+                    "as DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if not a.full:
+        a.no_decode = a.no_aux = a.no_prof = a.no_cpu_baseline = a.no_fp8 = a.no_e2e = True
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1103,7 +1134,8 @@ def main():
     lib = _lib.load()                 # raises when the HIP library is missing: there is no other compute path
     a.pipeline = not a.no_pipeline
     sched_pick = None
-    if a.batch <= 0:
+    picked = a.batch <= 0
+    if picked:
         # The tower schedule is picked by measurement, not by a constant (one pipelined lane of 28 frames was 2.7 % faster than
         # two lanes of 28 on the builder's box, 3 % slower on others).  Both candidates run the SAME 56 frames per step over the same stream; untimed,
         # before the warm-up; two interleaved rounds, best of each.
@@ -1126,8 +1158,12 @@ def main():
     cfg = PathConfig(llm_layers=0 if a.no_decode else 32, max_frames_per_call=B, vit_fp16=a.vit_fp16)
     # BASELINE configs[1] names a 60 s x 30 fps stream: the pool is ALWAYS those 1800 frames, and the timed region is about one pass
     # over it whatever --steps the caller picks -- a step is `cps` calls of B frames (steps x cps x B ~ 1800; the walk wraps around)
-    n_pool = max(B, a.stream_frames)
-    cps = max(1, int(round(n_pool / float(a.steps * B))))
+    # A step is sized in units of 56 frames when the schedule was picked here (one call of 56 or two of 28), so the frames every step
+    # walks -- and with them what --dump-outputs writes -- do not depend on the pick; with --batch the unit is that batch.
+    unit = 56 if picked else B
+    n_pool = max(unit, a.stream_frames)
+    cps = max(1, min(int(round(n_pool / float(a.steps * unit))), n_pool // unit)) * (unit // B)
+    FS = B * cps                                      # frames per step
     if plumbing:
         model, frames, stream = None, torch.zeros(n_pool, 1, 1, 3, dtype=torch.uint8), _PlumbingStream(cfg.conn_d_model)
     else:
@@ -1141,14 +1177,15 @@ def main():
     sync()
 
     def step(i):
-        out = None
+        outs = []                        # what every call of the step returns: (gate logits, decisions)
+        base = (i * FS) % (n_pool - FS + 1)
         for c in range(cps):
-            off = ((i * cps + c) * B) % (n_pool - B + 1)
+            off = base + c * B
             if not a.pipeline:
-                out = stream.push_frames(frames[off:off + B])
+                outs.append(stream.push_frames(frames[off:off + B]))
             else:
-                out = stream.push_frames_pipelined(frames[off:off + B])      # same results; the gate pass of call i overlaps the tower of call i+1
-        return out
+                outs.append(stream.push_frames_pipelined(frames[off:off + B]))      # same results; the gate pass of call i overlaps the tower of call i+1
+        return outs
 
     # N > 1 (BASELINE configs[3]): every step is one exchange tick.  Ranks "fire" on DIFFERENT, rank-specific steps (the random
     # gate's own decisions are not a workload): on its fire steps a rank contributes the frame tokens of the segment since its
@@ -1243,7 +1280,7 @@ def main():
     for i in range(a.steps):
         if prof_in_timed and i == a.steps - prof_steps:
             lib.sm_prof_enable(1)
-        logits, dec = step(a.warmup + i)
+        last_outs = step(a.warmup + i)
         if ex is not None:
             exchange(a.warmup + i)
     stream.join()                        # the last step's connector + gate pass is inside the timed region
@@ -1257,6 +1294,9 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     dt_local = dt
+    logits, dec = last_outs[-1]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_outs, stream.tokens(stream.num_frames - FS, FS))
     gemm_prof = None
     if prof and not prof_in_timed:
         prof_steps = 12

@@ -2,7 +2,7 @@
 # same-box A/B of cache-policy variants of the streamed GEMM outputs (common.h store16_stream; tools/build_variant.sh NAME '-DSM_STREAM_STORE_MODS="sc1 nt"'):
 #   gpurun -- 'VARIANTS="main nt1" BATCH=56 bash tools/nt_store_ab.sh'
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out/${TAG:-r06k}
-BENCH_FAST="--no-cpu-baseline --no-decode --no-aux --no-e2e --no-fp8"
+BENCH_FAST="--full --no-cpu-baseline --no-decode --no-aux --no-e2e --no-fp8"
 for i in 1 2; do for v in ${VARIANTS:-main nt1 nt2 nt3}; do for B in ${BATCH:-28}; do
   L=$GRAFT_REPO_ROOT/streammind_amd/lib/libstreammind_hip.so; [ "$v" != main ] && L=$GRAFT_REPO_ROOT/streammind_amd/lib/libstreammind_hip_$v.so
   STREAMMIND_HIP_LIB=$L timeout 600 python bench.py $BENCH_FAST ${EXTRA:-} --batch $B 2>/dev/null | python -c "

@@ -12,7 +12,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 2400 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log | tee $O/pytest_gpu_tail.txt
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $O/pytest_gpu_tail.txt
 fi
-timeout 900 python bench.py > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log > $O/bench_default.json; cut -c1-300 $O/bench_default.json
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log > $O/bench_default.json; cut -c1-300 $O/bench_default.json
 # kernel trace of the bench STEPS, single-lane plain schedule (the schedule of the line's `roofline` segment): default path (bf16: LayerNorm launches) ...
 rm -rf /tmp/p1; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python bench.py --batch 28 --no-pipeline --steps 20 --warmup 2 $STEPS > $O/bench_steps_profiled.log 2>&1
 grep '^{"metric"' $O/bench_steps_profiled.log > $O/bench_steps_profiled.json; cp "$(find /tmp/p1 -name '*kernel_stats.csv' | head -1)" $O/bench_steps_kernel_stats.csv

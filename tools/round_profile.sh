@@ -6,7 +6,7 @@ ulimit -c 0
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/round; mkdir -p $O; export TAG=round
 timeout 2400 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-timeout 900 python bench.py > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log > $O/bench_default.json; cut -c1-400 $O/bench_default.json
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log > $O/bench_default.json; cut -c1-400 $O/bench_default.json
 # kernel stats of the BENCH STEPS ONLY (no decode / end-to-end / auxiliary legs, no HIP-event bracketing).  Two runs:
 #  (a) the default schedule (56 frames per step, two tower lanes + pipelined gate pass): two kernels share the chip, so a kernel's
 #      duration here includes the time its blocks waited for CUs the other lane's kernel held;
@@ -50,7 +50,7 @@ for CG in 0 3; do
   rm -rf /tmp/pmc_f$CG; SM_GEMM_CG=$CG rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_f$CG -- python bench.py --batch 28 --no-pipeline --steps 3 --warmup 1 --stream-frames 112 --no-cpu-baseline --no-decode --no-prof --no-aux > /dev/null 2>&1
   rm -rf /tmp/pmc_w$CG; SM_GEMM_CG=$CG rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_w$CG -- python bench.py --batch 28 --no-pipeline --steps 3 --warmup 1 --stream-frames 112 --no-cpu-baseline --no-decode --no-prof --no-aux > /dev/null 2>&1
   python tools/pmc_traffic_summary.py /tmp/pmc_f$CG /tmp/pmc_w$CG $O/gemm_traffic_cg$CG.json
-  SM_GEMM_CG=$CG timeout 600 python bench.py --batch 28 --no-pipeline --no-cpu-baseline --no-decode --no-aux --no-e2e --no-fp8 2>/dev/null | grep '^{"metric"' > $O/bench_single_lane_cg$CG.json
+  SM_GEMM_CG=$CG timeout 600 python bench.py --full --batch 28 --no-pipeline --no-cpu-baseline --no-decode --no-aux --no-e2e --no-fp8 2>/dev/null | grep '^{"metric"' > $O/bench_single_lane_cg$CG.json
 done
 python - <<'PY'
 import json

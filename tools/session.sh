@@ -4,7 +4,7 @@
 set -u
 ulimit -c 0
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-BENCH_FAST="--no-cpu-baseline --no-decode --no-aux --no-e2e --no-fp8"
+BENCH_FAST="--full --no-cpu-baseline --no-decode --no-aux --no-e2e --no-fp8"
 line() { python -c "
 import sys, json
 for l in sys.stdin:
@@ -70,7 +70,7 @@ for f in ('two_lanes', 'single_lane'):
     d = json.load(open('$O/bench_%s_fold$L.json' % f))['roofline']['by_shape']
     print('   by_shape', f, {k: v['avg_launch_us'] for k, v in d.items()})"
   done | tee $O/fold_ab${EXTRA:+_fp16}.txt ;;
-bench)        timeout 900 python bench.py 2>/dev/null | grep '^{"metric"' > $O/bench_default.json; cut -c1-600 $O/bench_default.json ;;
+bench)        timeout 900 python bench.py --full 2>/dev/null | grep '^{"metric"' > $O/bench_default.json; cut -c1-600 $O/bench_default.json ;;
 *) echo "unknown step $STEP" ;;
 esac
 done
