@@ -423,6 +423,29 @@ int sm_llm_decode(sm_stream* s, int n_steps, int32_t* out_ids_dev, void* stream)
  * sm_stream_logits (HF generate with do_sample=True: serve/model_worker.py:247-282 passes temperature / top_p); the next
  * sm_llm_decode step emits and feeds back THIS token */
 int sm_stream_set_next_token(sm_stream* s, const int32_t* tok_dev, void* stream);
+/* Device-side sampling (csrc/sample.hip; replaces the host-side sort + softmax + cumsum + multinomial of HF generate(do_sample=True)).
+ * The rule, for a row l[0..V) and (temperature T > 0, top_k >= 0, 0 < top_p <= 1), HF's warper order (temperature, top-k, top-p):
+ *   x_v = (l_v - max l) / T, e_v = exp(x_v), p_v = e_v / sum e; above(v) = sum of p_w over l_w > l_v (strictly); rank(v) = #{w: l_w > l_v};
+ *   v is kept iff (top_k == 0 or rank(v) < top_k) and (top_p >= 1 or above(v) < top_p): TopPLogitsWarper with min_tokens_to_keep = 1, independent of
+ *   the sort order -- tokens with EQUAL logits are kept or dropped together (the only difference from HF, at an exact tie on the boundary); top-p uses the
+ *   softmax over the FULL row (HF renormalises over the top-k survivors first when top_k > 0); the top token is always kept.
+ *   With u in [0, 1) and Z = sum of e_v over the kept tokens, the token is the first v in token-id order whose inclusive kept-CDF exceeds u * Z (the last kept
+ *   token with mass if rounding runs off the end).  -inf logits have mass 0 and are never chosen; rows holding NaN or +inf are unsupported.
+ *   u is the caller's or Philox4x32-10: key = (seed low 32 bits, seed high 32 bits), counter = (pos low, pos high, 0, 0), u = (out[0] >> 8) * 2^-24, with
+ *   pos = the absolute context index the chosen token will occupy -- a stream's ids do not depend on how a reply is cut into n_steps calls, on single
+ *   versus batched decode (given equal logits) or on KV prefix reuse.  Results are bit-reproducible from run to run (integer sums throughout). */
+typedef struct sm_sampling_t { float temperature; float top_p; int32_t top_k; int32_t reserved; uint64_t seed; } sm_sampling_t;
+/* operator: M rows of logits fp32 [M][ld]; params_host: one sm_sampling_t for all rows (n_params == 1) or one per row (n_params == M);
+ * u_dev_opt fp32 [M] or NULL -> Philox(seed of the row, pos_host[m]) (pos_host may be NULL when u is given); tok_out int32 [M]; optionally the number of
+ * kept tokens int32 [M] and their share of the row's mass Z / sum e fp32 [M].  SM_EINVAL for temperature <= 0, top_p <= 0, top_k < 0, V < 1. */
+int sm_sample_rows(const float* logits, int M, int V, int ld, const sm_sampling_t* params_host, int n_params,
+                   const int64_t* pos_host, const float* u_dev_opt, int32_t* tok_out, int32_t* kept_out_opt,
+                   float* kept_mass_out_opt, void* stream);
+/* per-stream rule for the pending token of sm_llm_prefill / sm_llm_forward_logits / sm_llm_decode / sm_group_llm_decode;
+ * NULL or temperature <= 0 -> greedy (the default: results are bit-identical to those without this call).  sm_stream_reset keeps the rule;
+ * sm_stream_set_next_token still overrides the pending token. */
+int sm_stream_set_sampling(sm_stream* s, const sm_sampling_t* p);
+int sm_stream_get_sampling(sm_stream* s, sm_sampling_t* out);      /* temperature 0 in *out: greedy */
 /* last-position logits of the most recent prefill/decode step: device fp32 [vocab] */
 const float* sm_stream_logits(sm_stream* s);
 /* async device-to-device copies out of the stream's own storage (tokens [t0, t0+n) x d_model fp32; vocabulary

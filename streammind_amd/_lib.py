@@ -52,6 +52,10 @@ class sm_config_t(C.Structure):
     ]
 
 
+class sm_sampling_t(C.Structure):
+    _fields_ = [("temperature", f32), ("top_p", f32), ("top_k", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
 class sm_jpeg_huff_t(C.Structure):
     _fields_ = [("fast", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 17), ("vals", C.c_uint8 * 256)]
 
@@ -134,6 +138,9 @@ SIGNATURES = {
     "sm_llm_decode": (i32, [vp, i32, vp, vp]),
     "sm_stream_set_next_token": (i32, [vp, vp, vp]),
     "sm_stream_logits": (vp, [vp]),
+    "sm_sample_rows": (i32, [vp, i32, i32, i32, C.POINTER(sm_sampling_t), i32, C.POINTER(C.c_int64), vp, vp, vp, vp, vp]),
+    "sm_stream_set_sampling": (i32, [vp, C.POINTER(sm_sampling_t)]),
+    "sm_stream_get_sampling": (i32, [vp, C.POINTER(sm_sampling_t)]),
     "sm_stream_read_tokens": (i32, [vp, i32, i32, vp, vp]),
     "sm_stream_read_state": (i32, [vp, vp, vp, vp]),
     "sm_stream_read_logits": (i32, [vp, vp, vp, vp]),

@@ -12,9 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libstreammind_hip.so")
-SOURCES = ["linear.hip", "gemm256.hip", "wstream.hip", "gemm_fp8.hip", "attention.hip", "vecops.hip", "ingest.hip", "stc.hip", "comm.hip", "jpeg.hip", "model.hip"]
+SOURCES = ["linear.hip", "gemm256.hip", "wstream.hip", "gemm_fp8.hip", "attention.hip", "vecops.hip", "ingest.hip", "stc.hip", "comm.hip", "jpeg.hip", "sample.hip", "model.hip"]
 HEADERS = ["common.h", "host.h", "linear_common.h", os.path.join("..", "..", "include", "streammind_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
+# per-source additions: the sampling kernels are built without packed fp32 arithmetic (v_pk_*_f32), so their fixed-point masses come from scalar fp32 ops only
+EXTRA_FLAGS = {"sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(src: str, dst: str) -> bool:
@@ -34,7 +36,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
         if force or _newer(src, obj) or any(_newer(h, obj) for h in hdr_paths):
-            cmd = [hipcc, *FLAGS, "-c", src, "-o", obj]
+            cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(s, []), "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((s, subprocess.Popen(cmd)))

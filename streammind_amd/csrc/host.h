@@ -106,6 +106,19 @@ int sm_linear_reserve(hipStream_t st, size_t slab_bytes, size_t dual_bytes);
 int sm_embed_tokens_seg_big(const SmTokPtrsBig& tok, int S, const void* table_bf16, int D, float* out, const SmTokPtrsBig& out_rows, int col, int f16, void* stream);
 int sm_argmax_rows_seg_big(const float* logits, int S, int V, int ld, const SmTokPtrsBig& out, void* stream);
 
+// sample.hip: device-side temperature / top-k / top-p sampling (the rule and the kernel plan stand at the head of that file).  One rule per row: what
+// sm_sampling_t says, prepared for the kernel (1 / T), plus the absolute context index the chosen token will occupy (the Philox counter); greedy != 0:
+// the row takes the arg-max branch of the launch.  Rules and token words travel by value up to SM_MAX_SEG rows, as a device-side table beyond
+// (pos of a table row = its pos when the call started + step).
+struct SmSampleRule { float inv_t, top_p; int32_t top_k, greedy; uint64_t seed; int64_t pos; };
+struct SmSamplePack { SmSampleRule r[SM_MAX_SEG]; int32_t* tok[SM_MAX_SEG]; };
+struct SmSampleTab { const SmSampleRule* r; int32_t* const* tok; int step; };
+int sm_sampling_check(const sm_sampling_t* p, const char* who);
+SmSampleRule sm_sample_rule(const sm_sampling_t* p, int64_t pos);          // p == NULL or temperature <= 0: greedy
+int sm_sample_tail(const float* logits, int V, const SmSampleRule& rule, int32_t* next_tok, int32_t* emit, const void* table, int D, float* emb, int f16, void* stream);
+int sm_sample_rows_seg(const float* logits, int S, int V, int ld, const SmSamplePack& pk, void* stream);
+int sm_sample_rows_tab(const float* logits, int S, int V, int ld, const SmSampleTab& tab, void* stream);
+
 // Optional in-library kernel timing (bench.py's roofline leg): when a class bit is enabled, every launch of that
 // class is bracketed by HIP events recorded ON THE LAUNCH STREAM; sm_prof_read() synchronises and sums.
 enum { SM_PROF_GEMM = 0, SM_PROF_SKINNY = 1, SM_PROF_ATTN = 2, SM_PROF_NCLS = 3 };

@@ -899,6 +899,8 @@ struct sm_stream {
     std::vector<DevBuf> kc, vtc;
     int cap = 0;
     DevBuf lmlog, next_tok;
+    sm_sampling_t samp = {0.f, 1.f, 0, 0, 0};     // how the pending token is chosen (sm_stream_set_sampling); temperature 0 = greedy
+    bool sampled() const { return samp.temperature > 0.f; }
     // pipelined perception (sm_stream_push_frames_pipelined): the connector + gate pass of call i runs on this stream's own
     // side HIP stream while the caller's stream already runs the tower of call i+1
     hipStream_t side = nullptr;
@@ -1059,6 +1061,18 @@ extern "C" int sm_stream_kv_len(sm_stream* s) { return s ? s->kv_len : -1; }
 extern "C" int sm_stream_set_kv_len(sm_stream* s, int n) {
     SM_REQUIRE(s && n >= 0 && n <= s->kv_len, "sm_stream_set_kv_len: %d outside [0, kv_len]", n);
     s->kv_len = n;
+    return SM_OK;
+}
+extern "C" int sm_stream_set_sampling(sm_stream* s, const sm_sampling_t* p) {
+    SM_REQUIRE(s && s->m->c.llm_layers > 0, "sm_stream_set_sampling: null stream / perception-only model");
+    if (!p || !(p->temperature > 0.f)) { s->samp = sm_sampling_t{0.f, 1.f, 0, 0, 0}; return SM_OK; }
+    { int rc = sm_sampling_check(p, "sm_stream_set_sampling"); if (rc) return rc; }
+    s->samp = *p;
+    return SM_OK;
+}
+extern "C" int sm_stream_get_sampling(sm_stream* s, sm_sampling_t* out) {
+    SM_REQUIRE(s && out, "sm_stream_get_sampling: null arg");
+    *out = s->samp;
     return SM_OK;
 }
 extern "C" const float* sm_stream_logits(sm_stream* s) { return s ? s->lmlog.as<float>() : nullptr; }
@@ -1285,6 +1299,7 @@ struct sm_stream_group {
     ConnScratch w;
     // batched decode scratch (rows = streams), allocated by the first sm_group_llm_decode
     DevBuf d_emb, d_xnb, d_xn32, d_qkvf, d_qb, d_ctxb, d_actb, d_log, d_ws;
+    DevBuf d_samp;               // > SM_MAX_SEG streams with a sampled one among them: [S] rules, [S] pending-token words (SmSampleTab), uploaded once per call
     DevBuf d_tab;                // > SM_MAX_SEG streams: [layers][S] K pointers, [layers][S] V^T pointers, [S] start positions (SmDecodeSegTab), uploaded once per call
     bool d_ready = false;
 };
@@ -1417,7 +1432,8 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
     return SM_OK;
 }
 
-// final norm + lm_head on row `row` of the residual stream, greedy argmax into next_tok; decode steps pass where the NEXT step's
+// final norm + lm_head on row `row` of the residual stream, greedy argmax (or the stream's sampling rule, sample.hip: the token will sit at context
+// index kv_len, which the layers have advanced already) into next_tok; decode steps pass where the NEXT step's
 // output id goes and ask for its embedding row in W->emb (row 0) -- nullptr / false after a prefill and on the last step
 static int llm_head(sm_stream* s, sm_model::LlmWs* W, int row, void* stream, int32_t* emit_next = nullptr, bool embed_next = false) {
     sm_model* m = s->m;
@@ -1432,6 +1448,9 @@ static int llm_head(sm_stream* s, sm_model::LlmWs* W, int row, void* stream, int
     if (fuse_norm) { a.norm_gamma = m->R.llm_norm; a.norm_eps = c.llm_eps; }
     a.out_f32 = s->lmlog.as<float>(); a.ldo = c.llm_vocab;
     if ((rc = sm_linear(&a, stream))) return rc;
+    if (s->sampled())
+        return sm_sample_tail(s->lmlog.as<float>(), c.llm_vocab, sm_sample_rule(&s->samp, s->kv_len), s->next_tok.as<int32_t>(), emit_next, m->R.embed->buf.p, ld,
+                              embed_next ? W->emb.as<float>() : nullptr, f16, stream);
     if (!emit_next && !embed_next) return sm_argmax(s->lmlog.as<float>(), c.llm_vocab, s->next_tok.as<int32_t>(), stream);
     argmax_emit_embed_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(s->lmlog.as<float>(), c.llm_vocab, s->next_tok.as<int32_t>(), emit_next,
                                                                  m->R.embed->buf.as<bf16_t>(), ld, embed_next ? W->emb.as<float>() : nullptr, f16);
@@ -1480,6 +1499,7 @@ extern "C" int sm_llm_forward_logits(sm_stream* s, const int32_t* ids, int n, fl
     }
     // keep the stream's "pending token / last logits" state what a prefill would have left
     SM_HIP(hipMemcpyAsync(s->lmlog.p, logits + (size_t)(n - 1) * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (s->sampled()) return sm_sample_tail(s->lmlog.as<float>(), V, sm_sample_rule(&s->samp, s->kv_len), s->next_tok.as<int32_t>(), nullptr, nullptr, 0, nullptr, 0, stream);
     return sm_argmax(s->lmlog.as<float>(), V, s->next_tok.as<int32_t>(), stream);
 }
 
@@ -1587,6 +1607,23 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
         SM_HIP(hipMemcpyAsync((char*)g->d_tab.p + 2 * np * sizeof(void*), hpos.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
         SM_HIP(hipStreamSynchronize((hipStream_t)stream));            // the host vectors go out of scope; once per call, not per step
         tab_kc = (void* const*)g->d_tab.p; tab_vtc = tab_kc + np; tab_pos0 = (const int*)((char*)g->d_tab.p + 2 * np * sizeof(void*));
+    }
+    // streams with a sampling rule (sm_stream_set_sampling): the arg-max stage of every step becomes ONE launch of the sampling kernel over all rows -- greedy
+    // streams of the group take its arg-max branch.  Rules + token words by value up to SM_MAX_SEG streams, as a device-side table (uploaded here, once) beyond.
+    // A group without a sampled stream keeps the arg-max launches.
+    bool any_sampled = false;
+    for (sm_stream* s : act) any_sampled = any_sampled || s->sampled();
+    SmSampleTab samp_tab = {nullptr, nullptr, 0};
+    if (any_sampled && NC > 1) {
+        std::vector<SmSampleRule> hr(S);
+        std::vector<int32_t*> ht(S);
+        for (int t = 0; t < S; ++t) { hr[t] = sm_sample_rule(&act[t]->samp, act[t]->kv_len); ht[t] = act[t]->next_tok.as<int32_t>(); }
+        const size_t rb = (size_t)S * sizeof(SmSampleRule), bytes = rb + (size_t)S * sizeof(int32_t*);
+        if (g->d_samp.bytes < bytes) { SM_HIP(hipStreamSynchronize((hipStream_t)stream)); if ((rc = g->d_samp.alloc(bytes))) return rc; }
+        SM_HIP(hipMemcpyAsync(g->d_samp.p, hr.data(), rb, hipMemcpyHostToDevice, (hipStream_t)stream));
+        SM_HIP(hipMemcpyAsync((char*)g->d_samp.p + rb, ht.data(), bytes - rb, hipMemcpyHostToDevice, (hipStream_t)stream));
+        SM_HIP(hipStreamSynchronize((hipStream_t)stream));            // the host vectors go out of scope; once per call, not per step
+        samp_tab.r = (const SmSampleRule*)g->d_samp.p; samp_tab.tok = (int32_t* const*)((char*)g->d_samp.p + rb);
     }
     auto c0 = [&](int ch) { return ch * SM_MAX_SEG; };
     auto cn = [&](int ch) { return S - c0(ch) < SM_MAX_SEG ? S - c0(ch) : SM_MAX_SEG; };
@@ -1704,7 +1741,16 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
             if (fuse_norm) { a.norm_gamma = m->R.llm_norm; a.norm_eps = c.llm_eps; }
             a.out_f32 = g->d_log.as<float>(); a.ldo = V;
             if ((rc = sm_linear(&a, stream))) return rc; }
-        if (NC > 1) {
+        if (any_sampled) {               // (kv_len has been advanced: it is the index the chosen token will occupy)
+            if (NC > 1) {
+                samp_tab.step = j + 1;
+                if ((rc = sm_sample_rows_tab(g->d_log.as<float>(), S, V, V, samp_tab, stream))) return rc;
+            } else {
+                SmSamplePack pk;
+                for (int t = 0; t < S; ++t) { pk.r[t] = sm_sample_rule(&act[t]->samp, act[t]->kv_len); pk.tok[t] = act[t]->next_tok.as<int32_t>(); }
+                if ((rc = sm_sample_rows_seg(g->d_log.as<float>(), S, V, V, pk, stream))) return rc;
+            }
+        } else if (NC > 1) {
             for (int b0 = 0; b0 < S; b0 += SM_BIG_SEG) {
                 const int bn = S - b0 < SM_BIG_SEG ? S - b0 : SM_BIG_SEG;
                 SmTokPtrsBig tok;

@@ -388,20 +388,33 @@ class Videollama2MistralForCausalLM:
 
     @torch.no_grad()
     def _generate_iter(self, seq: List[int], max_new_tokens: int, stopping_criteria=None, do_sample: bool = False,
-                       temperature: float = 1.0, top_p: float = 1.0, generator=None):
-        """yields the new ids in chunks (what a TextIteratorStreamer consumer sees); the concatenation is `_generate`'s list"""
-        max_new_tokens = self._begin_generate(seq, max_new_tokens)
-        out: List[int] = []
-        done = False
-        while not done and len(out) < max_new_tokens:
-            if do_sample:                                     # one step at a time: the choice needs this position's logits
-                self.stream.set_next_token(self._sample(temperature, top_p, generator))
-                n = 1
-            else:
-                n = min(self.decode_chunk, max_new_tokens - len(out))
-            ids = self.stream.decode(n).cpu().tolist()          # n speculative greedy steps, one host sync
-            fresh, done = self._accept_tokens(out, ids, len(seq), stopping_criteria)
-            yield fresh
+                       temperature: float = 1.0, top_p: float = 1.0, generator=None, device_sampling: bool = False, top_k: int = 0,
+                       seed: int = 0):
+        """yields the new ids in chunks (what a TextIteratorStreamer consumer sees); the concatenation is `_generate`'s list.
+        do_sample + device_sampling: the stream carries the sampling rule (NativeStream.set_sampling: temperature / top-k / top-p on
+        the GPU, uniforms from Philox(seed, context index)), so a sampled reply decodes `decode_chunk` steps per host sync like a
+        greedy one and its ids do not depend on the chunking; the rule is cleared when the reply ends."""
+        on_device = bool(do_sample and device_sampling)
+        if on_device and generator is not None:
+            raise ValueError("device_sampling draws from Philox(seed, position) on the GPU: pass `seed`, not a torch `generator`")
+        if on_device:                                         # before the prefill: its pending token is the reply's first sampled id
+            self.stream.set_sampling(temperature, top_p=top_p, top_k=top_k, seed=seed)
+        try:
+            max_new_tokens = self._begin_generate(seq, max_new_tokens)
+            out: List[int] = []
+            done = False
+            while not done and len(out) < max_new_tokens:
+                if do_sample and not on_device:                   # one step at a time: the choice needs this position's logits
+                    self.stream.set_next_token(self._sample(temperature, top_p, generator))
+                    n = 1
+                else:
+                    n = min(self.decode_chunk, max_new_tokens - len(out))
+                ids = self.stream.decode(n).cpu().tolist()          # n speculative steps (greedy or device-sampled), one host sync
+                fresh, done = self._accept_tokens(out, ids, len(seq), stopping_criteria)
+                yield fresh
+        finally:
+            if on_device:
+                self.stream.set_sampling(None)
 
     def _generate(self, seq: List[int], max_new_tokens: int, stopping_criteria=None, **sample_kw) -> List[int]:
         return [t for chunk in self._generate_iter(seq, max_new_tokens, stopping_criteria, **sample_kw) for t in chunk]
@@ -559,7 +572,8 @@ class Videollama2MistralForCausalLM:
             seq = [int(t) for t in ids]
         do_sample = bool(kwargs.get("do_sample", False))
         sample_kw = dict(do_sample=do_sample, temperature=float(kwargs.get("temperature") or 1.0), top_p=float(kwargs.get("top_p") or 1.0),
-                         generator=kwargs.get("generator")) if do_sample else {}
+                         generator=kwargs.get("generator"), device_sampling=bool(kwargs.get("device_sampling", False)),
+                         top_k=int(kwargs.get("top_k") or 0) if kwargs.get("device_sampling") else 0, seed=int(kwargs.get("seed") or 0)) if do_sample else {}
         streamer = kwargs.get("streamer")                 # HF streamer protocol: put(ids) per step, end() -- model_worker.py:263
         new_ids: List[int] = []
         if streamer is not None:                          # HF hands the (here empty: the inputs are embeddings) prompt ids over first
@@ -574,7 +588,8 @@ class Videollama2MistralForCausalLM:
 
     @torch.no_grad()
     def generate_iter(self, inputs: torch.Tensor, images_or_videos=None, modal_list=None, max_new_tokens: int = 1024, stopping_criteria=None,
-                      do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0, generator=None):
+                      do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0, generator=None, device_sampling: bool = False,
+                      top_k: int = 0, seed: int = 0):
         """`generate` as a generator of id chunks, for callers that forward text while it is produced (the serving worker): the
         native decode loop runs `decode_chunk` greedy steps per host sync and hands each accepted chunk over at once -- no second
         thread, no queue.  The concatenation of the chunks is `generate`'s result."""
@@ -587,7 +602,8 @@ class Videollama2MistralForCausalLM:
             seq, _, _, _ = self._splice_clips(ids, images_or_videos, modal_list or ["video"], features=False)
         else:
             seq = [int(t) for t in ids]
-        sample_kw = dict(do_sample=True, temperature=float(temperature or 1.0), top_p=float(top_p or 1.0), generator=generator) if do_sample else {}
+        sample_kw = dict(do_sample=True, temperature=float(temperature or 1.0), top_p=float(top_p or 1.0), generator=generator,
+                         device_sampling=bool(device_sampling), top_k=int(top_k or 0) if device_sampling else 0, seed=int(seed or 0)) if do_sample else {}
         yield from self._generate_iter(seq, int(max_new_tokens), stopping_criteria, **sample_kw)
 
     @torch.no_grad()

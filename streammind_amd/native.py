@@ -300,6 +300,21 @@ class NativeStream:
         assert tok.dtype == torch.int32 and tok.is_cuda and tok.numel() == 1
         check(self.lib.sm_stream_set_next_token(self.h, tok.data_ptr(), _stream()), "sm_stream_set_next_token")
 
+    def set_sampling(self, temperature: Optional[float], top_p: float = 1.0, top_k: int = 0, seed: int = 0) -> None:
+        """how prefill / forward_logits / decode (and a group decode this stream takes part in) choose the pending token from now on:
+        temperature / top-k / top-p on the GPU (sm_stream_set_sampling; the rule stands in include/streammind_hip.h), uniforms from
+        Philox(seed, context index).  None (or temperature <= 0): back to greedy, the default."""
+        if temperature is None:
+            check(self.lib.sm_stream_set_sampling(self.h, None), "sm_stream_set_sampling")
+            return
+        p = _lib.sm_sampling_t(float(temperature), float(top_p), int(top_k), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        check(self.lib.sm_stream_set_sampling(self.h, C.byref(p)), "sm_stream_set_sampling")
+
+    def get_sampling(self) -> Optional[dict]:
+        p = _lib.sm_sampling_t()
+        check(self.lib.sm_stream_get_sampling(self.h, C.byref(p)), "sm_stream_get_sampling")
+        return None if p.temperature <= 0 else dict(temperature=p.temperature, top_p=p.top_p, top_k=p.top_k, seed=p.seed)
+
     def logits(self) -> Tuple[torch.Tensor, torch.Tensor]:
         lg = torch.empty(self.model.cfg.llm_vocab, dtype=torch.float32, device=self.dev)
         nt = torch.empty(1, dtype=torch.int32, device=self.dev)
@@ -357,7 +372,7 @@ class NativeStreamGroup:
         return logits, dec
 
     def decode(self, n_steps: int, active: Optional[Sequence[bool]] = None) -> torch.Tensor:
-        """batched greedy decode of the (active) streams: int32 [S, n_steps]; rows of inactive streams are -1"""
+        """batched decode of the (active) streams -- greedy, or by each stream's own set_sampling rule: int32 [S, n_steps]; rows of inactive streams are -1"""
         S = len(self.streams)
         out = torch.full((S, n_steps), -1, dtype=torch.int32, device=self.dev)
         mask = None if active is None else (C.c_int32 * S)(*[int(bool(a)) for a in active])
@@ -426,6 +441,29 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int 
     check(lib.sm_cross_entropy(logits.data_ptr(), n, V, logits.stride(0), labels.data_ptr(), ignore_index, nll.data_ptr(),
                                am.data_ptr(), _stream()), "sm_cross_entropy")
     return nll, am
+
+
+def sample_rows(logits: torch.Tensor, params, pos: Optional[Sequence[int]] = None, u: Optional[torch.Tensor] = None,
+                return_kept: bool = False):
+    """temperature / top-k / top-p sampling of every row of fp32 logits [M, V] on the GPU (sm_sample_rows).  params: one
+    (temperature, top_p, top_k, seed) tuple for all rows or a list of M; u: fp32 [M] uniforms in [0, 1), or None -> Philox(seed, pos[m]).
+    -> int32 [M] token ids (with return_kept: also the kept counts int32 [M] and the kept share of the mass fp32 [M])."""
+    lib = _lib.load()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    M, V = logits.shape
+    plist = [params] if isinstance(params, tuple) else list(params)
+    arr = (_lib.sm_sampling_t * len(plist))(*[_lib.sm_sampling_t(float(t), float(tp), int(tk), 0, int(sd) & 0xFFFFFFFFFFFFFFFF) for t, tp, tk, sd in plist])
+    if u is not None:
+        assert u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() == M
+    elif pos is None:
+        raise ValueError("sample_rows: give uniforms `u` or the positions `pos` for the device generator")
+    parr = None if pos is None else (C.c_int64 * M)(*[int(x) for x in pos])
+    tok = torch.empty(M, dtype=torch.int32, device=logits.device)
+    kept = torch.empty(M, dtype=torch.int32, device=logits.device) if return_kept else None
+    mass = torch.empty(M, dtype=torch.float32, device=logits.device) if return_kept else None
+    check(lib.sm_sample_rows(logits.data_ptr(), M, V, logits.stride(0), arr, len(plist), parr, _p(u), tok.data_ptr(), _p(kept), _p(mass), _stream()),
+          "sm_sample_rows")
+    return (tok, kept, mass) if return_kept else tok
 
 
 def set_vit_ln_fold(mode: int) -> None:

@@ -15,6 +15,7 @@ import argparse
 import asyncio
 import base64
 import json
+import os
 import contextlib
 import threading
 import time
@@ -80,7 +81,7 @@ class ModelWorker:
     def __init__(self, controller_addr, worker_addr, worker_id, no_register, model_path, model_base, model_name, load_8bit=False,
                  load_4bit=False, device="cuda", *, loaded=None, post: Callable = _http_post, limit_model_concurrency: int = 5,
                  start_heart_beat: bool = True, keywords=(), max_streams: int = 16, stream_idle_s: float = 600.0,
-                 stream_max_frames: int = 4096, clock: Callable = time.monotonic):
+                 stream_max_frames: int = 4096, clock: Callable = time.monotonic, device_sampling: bool = False):
         self.controller_addr, self.worker_addr, self.worker_id = controller_addr, worker_addr, worker_id
         self.model_path = model_path
         if model_name is None:
@@ -91,6 +92,7 @@ class ModelWorker:
         self.limit_model_concurrency = limit_model_concurrency
         self.model_semaphore: Optional[asyncio.Semaphore] = None
         self.global_counter = 0
+        self.device_sampling = bool(device_sampling)               # sampled requests choose their tokens on the GPU (generate_iter(device_sampling=True)); off by default
         self.keywords = [k for k in keywords if k]                 # assets/keywords.txt of the reference (:45-55); empty by default
         if loaded is None:
             from ..model.builder import load_pretrained_model
@@ -254,9 +256,14 @@ class ModelWorker:
                 text = text[:-len(stop_str)]
             return json.dumps({"text": text, "error_code": 0}).encode() + b"\0", False
 
+        sample_kw = {}
+        if self.device_sampling and temperature > 0.001:        # per-request seed: the request's own "seed", else 64 fresh bits
+            seed = params.get("seed")
+            sample_kw = {"device_sampling": True, "seed": int(seed) if seed is not None else int.from_bytes(os.urandom(8), "little")}
+
         def decode(put, cancelled):                          # under the model lock, on the producer thread: ids only
             for chunk in model.generate_iter(input_ids, max_new_tokens=budget, stopping_criteria=stops, do_sample=temperature > 0.001,
-                                             temperature=temperature, top_p=top_p, **clip_kw):
+                                             temperature=temperature, top_p=top_p, **sample_kw, **clip_kw):
                 put([int(t) for t in chunk])
                 if cancelled():
                     return
@@ -399,7 +406,9 @@ if __name__ == "__main__":
     ap.add_argument("--no-register", action="store_true")
     ap.add_argument("--load-8bit", action="store_true")
     ap.add_argument("--load-4bit", action="store_true")
+    ap.add_argument("--device-sampling", action="store_true", help="sampled requests (temperature > 0) choose their tokens on the GPU: "
+                    "decode_chunk steps per host sync; seed from the request's \"seed\" or os.urandom")
     a = ap.parse_args()
     w = ModelWorker(a.controller_address, a.worker_address, str(uuid.uuid4())[:6], a.no_register, a.model_path, a.model_base, a.model_name,
-                    a.load_8bit, a.load_4bit, a.device, limit_model_concurrency=a.limit_model_concurrency)
+                    a.load_8bit, a.load_4bit, a.device, limit_model_concurrency=a.limit_model_concurrency, device_sampling=a.device_sampling)
     uvicorn.run(create_app(w), host=a.host, port=a.port, log_level="info")

@@ -21,7 +21,7 @@ prompt contains that reply): replies, gate logits and the grown prompt are bit-i
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Iterable, Iterator, List, Optional, Tuple
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -289,14 +289,17 @@ class MultiStreamSession:
     reply ids are the greedy ids of the same logits up to fp32 summation order).  `models`: one
     Videollama2MistralForCausalLM per stream, all built on the SAME NativeModel."""
 
-    def __init__(self, models, tokenizer, max_new_tokens: int = 1024, decode_chunk: int = 16, continuous: bool = False):
+    def __init__(self, models, tokenizer, max_new_tokens: int = 1024, decode_chunk: int = 16, continuous: bool = False,
+                 sampling: Optional[Sequence[Optional[dict]]] = None):
         """continuous=False: a tick returns when the replies it started are complete (every stream waits for them: the lock-step form).
         continuous=True: replies stay IN FLIGHT across ticks -- a tick is one perception pass for every stream plus `decode_chunk` decode steps of all
         the streams that are replying at that moment, whichever tick started them (one weight pass per step for all of them: a reply of 256 tokens no
         longer stops the other streams' frames for 256 steps, and replies started ticks apart share their weight passes); a stream that fires again
         while it is still replying gets that reply right behind the running one, on the frame interval it fired at.  Perception does not depend on the
         replies (the gate reads the connector state only), so per stream the events are those of the lock-step form -- they are handed out by the tick
-        in which they complete; `flush()` finishes what is in flight."""
+        in which they complete; `flush()` finishes what is in flight.
+        sampling: per stream None (greedy) or dict(temperature=, top_p=, top_k=, seed=) -- that stream's replies are SAMPLED on the GPU
+        (NativeStream.set_sampling) and still decode through the batched call, next to the greedy streams of the group."""
         assert len(models) >= 1 and all(m.native is models[0].native for m in models), "the streams must share one NativeModel"
         self.models, self.tok = list(models), tokenizer
         self.native = models[0].native
@@ -305,6 +308,8 @@ class MultiStreamSession:
         self.prompts: List[Optional[str]] = [None] * len(models)
         self.stats = StreamStats()
         self.continuous = continuous
+        self.sampling = list(sampling) if sampling is not None else [None] * len(models)
+        assert len(self.sampling) == len(models), "one sampling entry (or None) per stream"
         self._replying = {}                                # stream index -> state of the reply in flight
         self._pending = [[] for _ in models]               # stream index -> frame positions of fires that wait for the running reply
 
@@ -352,6 +357,8 @@ class MultiStreamSession:
         m.interval_id_list.append(upto)
         input_ids = tokenizer_MMODAL_token(self.prompts[i], self.tok, MMODAL_TOKEN_INDEX["VIDEO"], return_tensors="pt").unsqueeze(0)
         seq = m._expand(input_ids[0].tolist())
+        if self.sampling[i]:                                # before the prefill: its pending token is the reply's first sampled id
+            m.stream.set_sampling(**self.sampling[i])
         budget = m._begin_generate(seq, self.max_new)
         self._replying[i] = {"seq_len": len(seq), "budget": budget, "out": [], "crit": [KeywordsStoppingCriteria(["</s>"], self.tok, input_ids)], "upto": upto}
 
@@ -370,6 +377,8 @@ class MultiStreamSession:
             _, done = self.models[i]._accept_tokens(st["out"], ids[i], st["seq_len"], st["crit"])
             if done or len(st["out"]) >= st["budget"]:
                 del self._replying[i]
+                if self.sampling[i]:
+                    self.models[i].stream.set_sampling(None)
                 text = self.tok.batch_decode([st["out"]], skip_special_tokens=True)[0].strip()
                 self.prompts[i] += " " + text + " </s>[INST] <video>\n [/INST]"          # video_score_stream_demo.py:124
                 events.append((i, StreamEvent(st["upto"], text, st["out"])))

@@ -128,6 +128,18 @@ def _(frames, pad_square, image_size):
     return frames.new_empty((frames.shape[0], image_size, image_size, 3))
 
 
+@torch.library.custom_op(f"{NS}::sample_rows", mutates_args=())
+def sample_rows(logits: Tensor, u: Tensor, temperature: float, top_p: float, top_k: int) -> Tensor:
+    """temperature / top-k / top-p sampling of every row of fp32 logits [M, V] with the caller's uniforms u [M] -> int32 [M]"""
+    from .native import sample_rows as _sample
+    return _sample(logits, (temperature, top_p, top_k, 0), u=u.to(torch.float32).contiguous())
+
+
+@sample_rows.register_fake
+def _(logits, u, temperature, top_p, top_k):
+    return logits.new_empty((logits.shape[0],), dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------ path level (handles as int64)
 @torch.library.custom_op(f"{NS}::vit_encode", mutates_args=())
 def vit_encode(model: int, frames_u8: Tensor, vit_hidden: int) -> Tensor:
@@ -213,5 +225,5 @@ def _(stream, n_steps, state):
     return state.new_empty((n_steps,), dtype=torch.int32)
 
 
-OPS = ("linear", "pack_weight", "norm", "vit_attention", "pool_rows", "ingest_frames", "vit_encode", "stream_push_frames",
+OPS = ("linear", "pack_weight", "norm", "vit_attention", "pool_rows", "ingest_frames", "sample_rows", "vit_encode", "stream_push_frames",
        "stream_push_pooled", "llm_prefill", "llm_decode")
