@@ -41,6 +41,7 @@ extern "C" {
 #define SM_W_BF16 0
 #define SM_W_FP8 1
 #define SM_W_FP8_MFMA 2   /* the SM_W_FP8 image; calls with > 16 rows quantise the activations per row to e4m3 and run fp8 x fp8 MFMA */
+#define SM_W_FP4 3        /* the sm_quant_pack_weight_fp4 image (OCP MXFP4: e2m1 codes + one e8m0 scale per 32 k, scales inside the image) */
 #define SM_OP_BF16 0  /* 16-bit operands (packed weights, x, 16-bit outputs) are bfloat16 */
 #define SM_OP_F16 1   /* ... IEEE half: tiled GEMM only (the ViT's optional fp16 mode = the reference demo's precision, builder.py:54) */
 #define SM_TILE_AUTO 0
@@ -63,6 +64,24 @@ int sm_pack_weight(const void* w_bf16, int N, int K, int ldw, void* out_packed, 
  * scale_out[N], fp8 image of sm_packed_fp8_bytes(N,K) bytes.  No reference counterpart (the reference is fp16/bf16). */
 size_t sm_packed_fp8_bytes(int N, int K);
 int sm_quant_pack_weight_fp8(const void* w_bf16, int N, int K, int ldw, void* out_packed_fp8, float* scale_out, void* stream);
+/* weight-only MXFP4 (OCP MX v1.0) for the LLM's linears (opt-in, sm_model_set_weights_fp4): blocks of 32 consecutive k of one output row share
+ * the scale X = 2^(floor(log2 max|w|) - 2), stored as an e8m0 byte (biased by 127; an all-zero block stores 127 and zero codes); elements are
+ * RNE(w / X) onto {0, +-0.5, +-1, +-1.5, +-2, +-3, +-4, +-6}, saturating at +-6.  K is padded with zero blocks to a multiple of 128, N to 16.
+ * ONE self-contained image of sm_packed_fp4_bytes(N, K) bytes, codes AND scale bytes (4.25 bits per weight; sm_linear_t.w_scale is unused for
+ * it).  Layout, per 16-row group rg, KS = ceil(K / 128): KS code chunks of 1 KiB -- lane (g, i) of chunk ks holds the 32 codes of
+ * W[rg*16 + i][ks*128 + g*32 ..+31], element 2b in the low nibble of byte b: a lane's 16-byte load is its A operand of one
+ * v_mfma_scale_f32_16x16x128_f8f6f4 -- then ceil(KS / 4) scale chunks of 256 B: byte h of lane (g, i)'s dword of chunk q is the scale of that
+ * lane's block in code chunk 4q + h (streammind_amd/csrc/common.h).  A fused image (q|k|v, gate|up) is the concatenation of its parts' row groups.
+ * sm_unpack_weight_fp4 writes row-major bf16 [N][ldo] of code x 2^(e - 127): every such value is exact in bf16.
+ *   sm_linear runs the image with w_dtype = SM_W_FP4: up to 16 rows on the block-scaled matrix instruction, the codes going from HBM into the
+ * matrix pipe with no conversion (gemm_fp4.hip; the activations enter as an e4m3 hi + lo pair per 32-block, about the precision of bf16: the
+ * mode is weight-only in effect); bias, act, fp32 residual, both outputs, the w2 dual and norm_gamma work, K % 32 == 0.  precise, x_rep,
+ * op_dtype = SM_OP_F16 and post_ln_* (up to 16 rows) are SM_EINVAL, and so is the fused RoPE + KV-append q|k|v product: an fp4 model runs the
+ * plain q|k|v product and then the RoPE / append launch.  More than 16 rows expand the image to a packed bf16 scratch per call (shared with
+ * the fp8 expansion) and run the bf16 kernels.  Measured against bf16 and fp8 weights at batch-1 decode: DESIGN.md, "MXFP4 weights". */
+size_t sm_packed_fp4_bytes(int N, int K);
+int sm_quant_pack_weight_fp4(const void* w_bf16, int N, int K, int ldw, void* out_packed_fp4, void* stream);
+int sm_unpack_weight_fp4(const void* packed_fp4, int N, int K, void* out_bf16, int ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Linear:  Y[M,N] = epilogue( X[M,K] . W[N,K]^T ).  Replaces every torch F.linear / cuBLAS GEMM+GEMV on
@@ -341,6 +360,11 @@ int sm_model_finalize(sm_model* m, void* stream);
 void sm_model_destroy(sm_model* m);
 /* weights_fp8 models: switch between weight-only fp8 (1) and fp8 x fp8 MFMA above 16 rows (2) at run time (same weight images) */
 int sm_model_set_fp8_mode(sm_model* m, int mode);
+/* MXFP4 weights (sm_quant_pack_weight_fp4) for the LLM's q|k|v, o, gate|up and down projections: 3.8 GB instead of 14.2 GB at Mistral-7B.  lm_head, the
+ * embedding table, the gate, the connector and the tower keep their formats.  Valid between sm_model_create and the first sm_model_load_tensor; exclusive
+ * with weights_fp8 and llm_fp16.  sm_llm_prefill / sm_llm_forward_logits expand the images per call above 16 rows, sm_llm_decode streams them as they are,
+ * sm_group_llm_decode takes up to 16 active streams (one pass of the weight stream) and refuses more up front. */
+int sm_model_set_weights_fp4(sm_model* m, int on);
 /* names of tensors still missing, '\n'-separated, into buf (for error messages) */
 int sm_model_missing(sm_model* m, char* buf, size_t buflen);
 

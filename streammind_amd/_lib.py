@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("STREAMMIND_HIP_LIB", LIB_PATH)
 
 SM_ACT_NONE, SM_ACT_QUICK_GELU, SM_ACT_LEAKY_RELU, SM_ACT_SOFTPLUS, SM_ACT_SILU, SM_ACT_GELU, SM_ACT_SWIGLU_DUAL = 0, 1, 2, 3, 4, 5, 6
 SM_X_BF16, SM_X_F32 = 0, 1
-SM_W_BF16, SM_W_FP8, SM_W_FP8_MFMA = 0, 1, 2
+SM_W_BF16, SM_W_FP8, SM_W_FP8_MFMA, SM_W_FP4 = 0, 1, 2, 3
 SM_OP_BF16, SM_OP_F16 = 0, 1
 SM_DT_BF16, SM_DT_F32, SM_DT_F16 = 0, 1, 2
 
@@ -78,6 +78,9 @@ SIGNATURES = {
     "sm_pack_weight": (i32, [vp, i32, i32, i32, vp, vp]),
     "sm_packed_fp8_bytes": (sz, [i32, i32]),
     "sm_quant_pack_weight_fp8": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "sm_packed_fp4_bytes": (sz, [i32, i32]),
+    "sm_quant_pack_weight_fp4": (i32, [vp, i32, i32, i32, vp, vp]),
+    "sm_unpack_weight_fp4": (i32, [vp, i32, i32, vp, i32, vp]),
     "sm_linear": (i32, [C.POINTER(sm_linear_t), vp]),
     "sm_norm": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, i32, vp]),
     "sm_norm_ex": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, i32, i32, vp]),
@@ -111,6 +114,7 @@ SIGNATURES = {
     "sm_model_finalize": (i32, [vp, vp]),
     "sm_model_destroy": (None, [vp]),
     "sm_model_set_fp8_mode": (i32, [vp, i32]),
+    "sm_model_set_weights_fp4": (i32, [vp, i32]),
     "sm_model_missing": (i32, [vp, C.c_char_p, sz]),
     "sm_vit_encode": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "sm_vit_encode_pixels": (i32, [vp, vp, i32, i32, vp, vp, vp]),

@@ -12,11 +12,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libstreammind_hip.so")
-SOURCES = ["linear.hip", "gemm256.hip", "wstream.hip", "gemm_fp8.hip", "attention.hip", "vecops.hip", "ingest.hip", "stc.hip", "comm.hip", "jpeg.hip", "sample.hip", "model.hip"]
+SOURCES = ["linear.hip", "gemm256.hip", "wstream.hip", "gemm_fp8.hip", "gemm_fp4.hip", "attention.hip", "vecops.hip", "ingest.hip", "stc.hip", "comm.hip", "jpeg.hip", "sample.hip", "model.hip"]
 HEADERS = ["common.h", "host.h", "linear_common.h", os.path.join("..", "..", "include", "streammind_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 # per-source additions: the sampling kernels are built without packed fp32 arithmetic (v_pk_*_f32), so their fixed-point masses come from scalar fp32 ops only
-EXTRA_FLAGS = {"sample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# gemm_fp4.hip: the same policy for the MXFP4 quantiser and the e4m3 hi / lo requantiser, whose results are asserted exactly (the MX codes) or against a
+# bound derived from exact steps (power-of-two scaling, the residual x - hi): scalar fp32 ops only.  Nothing is known to break with packed ops -- it has not
+# been built that way -- and nothing is lost: the file's VALU work is conversions and compares, its hot loop loads and MFMAs
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"sample.hip": _NO_PK_F32, "gemm_fp4.hip": _NO_PK_F32}
 
 
 def _newer(src: str, dst: str) -> bool:

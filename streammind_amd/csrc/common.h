@@ -162,3 +162,12 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 __host__ __device__ __forceinline__ size_t packed_index(int n, int k, int KS) {
     return ((size_t)(n >> 4) * KS + (k >> 5)) * 512 + (size_t)((((k & 31) >> 3) << 4) + (n & 15)) * 8 + (k & 7);
 }
+
+// MXFP4 packed layout (SM_W_FP4; OCP MX v1.0: e2m1 codes, one e8m0 scale 2^(e - 127) per 32 consecutive k of an output row):
+//   W[N][K] bf16  ->  per 16-row group rg one contiguous stream of fp4_rg_bytes(KS) bytes, KS = ceil(K / 128) (N, K zero-padded to 16 / 128):
+//     codes   [ks 0..KS)[lane 0..63][16 B]      lane = g*16 + i holds the 32 codes of W[rg*16 + i][ks*128 + g*32 + 0..31] -- one MX
+//                                               block; element 2b in the low nibble of byte b -- i.e. one wave-wide 16-byte load is
+//                                               the A operand of v_mfma_scale_f32_16x16x128_f8f6f4 (cbsz 4) and 1 KiB contiguous
+//     scales  [q 0..ceil(KS/4))[lane 0..63][4 B] byte h of lane (g, i)'s dword = the e8m0 byte of ITS block of code chunk 4q + h
+//                                               (the lane that feeds scale_a holds its own scale; padding bytes are 127)
+__host__ __device__ __forceinline__ size_t fp4_rg_bytes(int KS) { return (size_t)KS * 1024 + (size_t)((KS + 3) >> 2) * 256; }

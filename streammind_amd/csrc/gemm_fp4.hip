@@ -1,0 +1,440 @@
+// MXFP4 (OCP MX v1.0: e2m1 elements, one e8m0 scale per 32 consecutive k of an output row) LLM weights: quantiser / packer,
+// unpacker, the bf16 expansion for calls with more than 16 rows, and the <= 16-row weight-streaming kernel on the CDNA4
+// block-scaled matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, A = e2m1 via cbsz 4, B = e4m3).
+//
+// Image (common.h, "MXFP4 packed layout"): per 16-row group one contiguous stream of KS = ceil(K / 128) code chunks of 1 KiB
+// -- lane (g, i) of chunk ks holds the 32 codes of W[rg*16 + i][ks*128 + g*32 .. +31], i.e. ONE MX block, 16 bytes, which is
+// exactly that lane's A operand of one MFMA -- followed by ceil(KS / 4) scale chunks of 256 B: lane (g, i)'s dword of scale
+// chunk q holds the e8m0 bytes of ITS blocks of code chunks 4q .. 4q+3 (byte h = chunk 4q + h), so the lane that feeds
+// scale_a receives the byte with one 4-byte load per four 16-byte loads.  4.25 bits per weight.
+// The instruction's operand map, measured with one-hot operands: an e2m1 operand (four registers) holds k = 32g .. 32g+31 of its
+// row in lane (g, i), in order; an e4m3 operand (eight registers) holds k = 16g .. 16g+15 in its first sixteen bytes and
+// k = 64 + 16g .. 64 + 16g+15 in the other sixteen; either way the scale operand of lane (G, i) applies to k = 32G .. 32G+31.
+// The weight image follows the first map, the requantised activations in LDS the second.
+//
+// The <= 16-row kernel.  Grid (row groups, K slices); a block owns one 16-row group and `qps` quads (a quad = four k-steps of
+// 128 = one scale dword) of K; its waves take the quads round robin and keep a register ring of D = 2 quads (8.25 KiB per wave
+// and matrix) in flight: all loads of a quad are issued before any is consumed, a consumed slot is refilled at once.  The
+// codes go from HBM into the matrix pipe as they are -- no conversion instruction on the hot path.
+//   The activations are the B operand.  Before the weight stream is consumed the block requantises its x rows (fp32 or
+// 16-bit, optionally RMS-normalised: norm_gamma) ONCE into LDS: every 32-block of a row becomes an e4m3 "hi" term with its own
+// e8m0 scale (block maximum scaled into [128, 256): no saturation) plus an e4m3 "lo" term, the RNE-rounded residual x - hi
+// with a scale of its own.  hi is round-to-nearest, so |x - hi| <= 2^-4 of x's binade and the signed residual carries four
+// more bits below that: |x - hi - lo| <= 2^-9 of the binade -- bf16's own rounding bound is 2^-8.  The mode is weight-only
+// in effect (unlike SM_W_FP8_MFMA, which rounds activations to e4m3).  Two MFMAs per weight fragment (hi, lo; four with the
+// SwiGLU dual image); matrix time stays far below the fragment's HBM time at these row counts.  The first x block of every
+// thread is fetched BEFORE the first weight loads (vmcnt retires in order), quantised while they fly; the barriers are raw
+// s_barriers (__syncthreads would drain the weight loads).
+//   LDS: 264 B per (k-step, row) of x (128 hi + 128 lo + 4 x 2 scale bytes), 44 KiB at most.  One row of K = 14336 needs
+// 29 KiB; where M x K does not fit (>= 6 rows at K = 4096) K is cut over blockIdx.y, the slices leave raw fp32 partial sums
+// in the split-K slabs and the shared slab-sum pass applies the epilogue (fixed slab order: deterministic).  The partial sums
+// of the waves of a block meet in LDS in wave order.
+//   Epilogue: store4 of linear_common.h (bias, act, fp32 residual, fp32 and / or 16-bit output, SwiGLU of the dual image).
+//   Measured (tools/decode_bench.py --fp4, Mistral-7B shapes, batch 1, one run on one box): 539.6 tokens/s against 523.4 on fp8 and 348.0
+// on bf16 weights -- 3 % faster than fp8, not the factor the bytes suggest.  The time is inside this kernel (1.81 of 1.85 ms per token in
+// the weight-streaming launches), which streams at 1.1 TB/s (q|k|v, o) to 2.8 TB/s (down) on its own bytes: it is the bound, not HBM.
+// Suspected, not yet traced: the x requantisation every block does before its first MFMA, the norm statistics' round trip, one block
+// per CU at N = 4096.  More than a few rows are not tuned -- a 16-stream batched decode step takes 5.7 ms against 3.0 ms on fp8 (one-wave
+// blocks, every block requantising all rows): DESIGN.md, "MXFP4 weights".  The memory saving -- 3.8 GB instead of 14.2 GB of LLM
+// linears -- stands either way.
+#include "linear_common.h"
+
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+
+// ------------------------------------------------------------------------------------------------ quantiser / packer
+// one thread = one lane slot of one code chunk = one MX block of 32 (zeros beyond N / K)
+__global__ void quant_pack_fp4_kernel(const bf16_t* __restrict__ w, int N, int K, int ldw, char* __restrict__ out, int KS, size_t total) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= total) return;
+    const int lane = (int)(c & 63);
+    const size_t rest = c >> 6;
+    const int ks = (int)(rest % KS), rg = (int)(rest / KS);
+    const int n = rg * 16 + (lane & 15), k0 = ks * 128 + (lane >> 4) * 32;
+    float v[32];
+    float am = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        v[j] = (n < N && k0 + j < K) ? bf2f(w[(size_t)n * ldw + k0 + j]) : 0.f;
+        am = fmaxf(am, fabsf(v[j]));
+    }
+    // X = 2^(floor(log2 max|w|) - 2), as the e8m0 byte; all-zero block: 127
+    int e = am > 0.f ? ilogbf(am) - 2 + 127 : 127;
+    e = e < 0 ? 0 : (e > 254 ? 254 : e);
+    uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        const float s = ldexpf(v[j], 127 - e);                        // w / X, exact
+        const float t = fabsf(s);
+        // RNE onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}: the grid's step is 0.5 below 2, 1 below 4, 2 above; ties go to the even code
+        float q = t < 2.f ? rintf(t * 2.f) * 0.5f : t < 4.f ? rintf(t) : rintf(t * 0.5f) * 2.f;
+        q = fminf(q, 6.f);                                            // saturate
+        uint32_t code = q < 2.f ? (uint32_t)(q * 2.f) : q < 4.f ? (uint32_t)q + 2u : (uint32_t)(q * 0.5f) + 4u;
+        if (s < 0.f && code) code |= 8u;
+        o[j >> 3] |= code << ((j & 7) * 4);                           // element 2b in the low nibble of byte b
+    }
+    char* rgp = out + (size_t)rg * fp4_rg_bytes(KS);
+    *(u32x4*)(rgp + (size_t)ks * 1024 + lane * 16) = u32x4{o[0], o[1], o[2], o[3]};
+    uint8_t* sp = (uint8_t*)(rgp + (size_t)KS * 1024 + (size_t)(ks >> 2) * 256 + lane * 4);
+    sp[ks & 3] = (uint8_t)e;
+    if (ks == KS - 1)
+        for (int h = (ks & 3) + 1; h < 4; ++h) sp[h] = 127;           // the padding of the last scale dword
+}
+
+extern "C" size_t sm_packed_fp4_bytes(int N, int K) {
+    return (size_t)((N + 15) / 16) * fp4_rg_bytes((K + 127) / 128);
+}
+
+extern "C" int sm_quant_pack_weight_fp4(const void* w, int N, int K, int ldw, void* out, void* stream) {
+    SM_REQUIRE(w && out && N > 0 && K > 0 && ldw >= K, "sm_quant_pack_weight_fp4: bad args N=%d K=%d ldw=%d", N, K, ldw);
+    const int KS = (K + 127) / 128;
+    const size_t total = (size_t)((N + 15) / 16) * KS * 64;
+    quant_pack_fp4_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>((const bf16_t*)w, N, K, ldw, (char*)out, KS, total);
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+
+// code (4 bits) x 2^(e - 127) as fp32: exact, and exact in bf16 too (two significant bits)
+__device__ __forceinline__ float fp4_value(uint32_t code, float scale) {
+    const uint32_t m = code & 1u, ex = (code >> 1) & 3u;
+    const float a = ex ? __uint_as_float(((126u + ex) << 23) | (m << 22)) : 0.5f * (float)m;
+    return (code & 8u) ? -a * scale : a * scale;
+}
+__device__ __forceinline__ float e8m0_value(uint32_t e) { return __uint_as_float(e ? e << 23 : 0x00400000u); }
+
+// PACKED = false: row-major bf16 [N][ldo]; PACKED = true: the packed bf16 image of common.h with KS32 = ceil(K / 32) k-steps
+// (what calls with more than 16 rows multiply with).  One thread = one MX block.
+template <bool PACKED>
+__global__ void unpack_fp4_kernel(const char* __restrict__ in, int N, int K, int KS, bf16_t* __restrict__ out, int ldo, size_t total) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= total) return;
+    const int lane = (int)(c & 63);
+    const size_t rest = c >> 6;
+    const int ks = (int)(rest % KS), rg = (int)(rest / KS);
+    const int i = lane & 15, g = lane >> 4;
+    const char* rgp = in + (size_t)rg * fp4_rg_bytes(KS);
+    const u32x4 q = *(const u32x4*)(rgp + (size_t)ks * 1024 + lane * 16);
+    const uint32_t sd = *(const uint32_t*)(rgp + (size_t)KS * 1024 + (size_t)(ks >> 2) * 256 + lane * 4);
+    const float sc = e8m0_value((sd >> ((ks & 3) * 8)) & 0xffu);
+    if constexpr (PACKED) {
+        const int KS32 = (K + 31) >> 5, ks32 = ks * 4 + g;
+        if (ks32 >= KS32) return;
+        u32x4* dst = (u32x4*)out + ((size_t)rg * KS32 + ks32) * 64 + i;
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {              // 8 elements = one dword of codes = one lane slot (gg, i) of the bf16 chunk
+            const uint32_t d = q[gg];
+            uint32_t o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = pack2bf(fp4_value((d >> (8 * j)) & 15u, sc), fp4_value((d >> (8 * j + 4)) & 15u, sc));
+            dst[gg * 16] = u32x4{o[0], o[1], o[2], o[3]};
+        }
+    } else {
+        const int n = rg * 16 + i, k0 = ks * 128 + g * 32;
+        if (n >= N) return;
+#pragma unroll
+        for (int j = 0; j < 32; ++j)
+            if (k0 + j < K) out[(size_t)n * ldo + k0 + j] = (bf16_t)f2bf(fp4_value((q[j >> 3] >> ((j & 7) * 4)) & 15u, sc));
+    }
+}
+
+extern "C" int sm_unpack_weight_fp4(const void* packed, int N, int K, void* out_bf16, int ldo, void* stream) {
+    SM_REQUIRE(packed && out_bf16 && N > 0 && K > 0 && ldo >= K, "sm_unpack_weight_fp4: bad args N=%d K=%d ldo=%d", N, K, ldo);
+    const int KS = (K + 127) / 128;
+    const size_t total = (size_t)((N + 15) / 16) * KS * 64;
+    unpack_fp4_kernel<false><<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>((const char*)packed, N, K, KS, (bf16_t*)out_bf16, ldo, total);
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+
+// fp4 image -> packed bf16 image of sm_packed_elems(N, K) elements (every slot written: padding rows / columns decode to zero)
+int launch_dequant_fp4(const void* w4, int N, int K, void* dst, hipStream_t st) {
+    const int KS = (K + 127) / 128;
+    const size_t total = (size_t)((N + 15) / 16) * KS * 64;
+    unpack_fp4_kernel<true><<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const char*)w4, N, K, KS, (bf16_t*)dst, 0, total);
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ activation requantiser
+__device__ __forceinline__ uint32_t pk4_fp8(float a, float b, float c, float d) {
+    int r = 0;
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, r, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
+    return (uint32_t)r;
+}
+// 32 consecutive k of one row -> e4m3 hi + e4m3 lo (the residual of hi), each with an e8m0 scale byte (sc16 = hi | lo << 8)
+__device__ __forceinline__ void quant32_hi_lo(float (&v)[32], uint32_t (&hi)[8], uint32_t (&lo)[8], uint32_t& sc16) {
+    float am = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) am = fmaxf(am, fabsf(v[j]));
+    // hi scale 2^(floor(log2 max) - 7): the block maximum lands in [128, 256), below e4m3's 448
+    int eh = (int)(__float_as_uint(am) >> 23) - 7;
+    eh = am > 0.f ? (eh < 1 ? 1 : eh) : 127;
+    const float inv = __uint_as_float((uint32_t)(254 - eh) << 23);
+    float am2 = 0.f;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        float s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = v[4 * d + j] * inv;
+        hi[d] = pk4_fp8(s[0], s[1], s[2], s[3]);
+        const f32x2 b0 = __builtin_amdgcn_cvt_pk_f32_fp8(hi[d], false), b1 = __builtin_amdgcn_cvt_pk_f32_fp8(hi[d], true);
+        v[4 * d] = s[0] - b0[0]; v[4 * d + 1] = s[1] - b0[1]; v[4 * d + 2] = s[2] - b1[0]; v[4 * d + 3] = s[3] - b1[1];      // exact
+#pragma unroll
+        for (int j = 0; j < 4; ++j) am2 = fmaxf(am2, fabsf(v[4 * d + j]));
+    }
+    // lo scale relative to hi's: 2^tl with the residual maximum in [128, 256) (it is at most 8: tl <= -4)
+    int tl = (int)(__float_as_uint(am2) >> 23) - 134;
+    const int tmin = eh < 100 ? -eh : -100;
+    tl = am2 > 0.f ? (tl < tmin ? tmin : tl) : 0;
+    const float inv2 = __uint_as_float((uint32_t)(127 - tl) << 23);
+#pragma unroll
+    for (int d = 0; d < 8; ++d) lo[d] = pk4_fp8(v[4 * d] * inv2, v[4 * d + 1] * inv2, v[4 * d + 2] * inv2, v[4 * d + 3] * inv2);
+    sc16 = (uint32_t)eh | ((uint32_t)(eh + tl) << 8);
+}
+
+// ------------------------------------------------------------------------------------------------ the <= 16-row kernel
+#define FP4_X_BYTES 264            // LDS bytes per (k-step, row): 128 hi + 128 lo + 4 x (hi, lo) scale bytes
+template <int WAVES, bool XF32, bool DUAL, bool NORM>
+__global__ __launch_bounds__(WAVES * 64) void skinny_fp4_kernel(LinArgs a, int qps, float* __restrict__ ws, float* __restrict__ ws2) {
+    static_assert(!NORM || XF32, "fused RMSNorm: fp32 activations");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int D = 2, PER = DUAL ? 8 : 4, NT = WAVES * 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rg = blockIdx.x, i = lane & 15, g = lane >> 4;
+    const int M = a.M, KS = (a.K + 127) >> 7, KQ = (KS + 3) >> 2;
+    const int q0 = blockIdx.y * qps, q1 = min(KQ, q0 + qps);
+    const int ks0 = q0 * 4, ksn = min(KS, q1 * 4) - ks0;              // k-steps of this block's K slice
+    float* const red = (float*)smem;                                    // [WAVES][PER][64] partial sums
+    float* const nsum = red + WAVES * PER * 64;                         // NORM: [16][WAVES] sums of squares
+    char* const xq = (char*)(nsum + (NORM ? 16 * WAVES : 0));           // [ksn][M][hi 128 | lo 128]
+    uint16_t* const xsc = (uint16_t*)(xq + (size_t)ksn * M * 256);      // [ksn][M][4]
+    const size_t rgb = fp4_rg_bytes(KS);
+    const char* const wrg = (const char*)a.w + (size_t)rg * rgb;
+    const char* const wrg2 = DUAL ? (const char*)a.w2 + (size_t)rg * rgb : nullptr;
+
+    // ---- x: one thread per 32-block b = (ksl * M + m) * 4 + gg of the slice
+    const int nblk = ksn * M * 4;
+    struct XRaw { std::conditional_t<XF32, f32x4, u32x4> v[XF32 ? 8 : 4]; };
+    auto x_load = [&](int b, XRaw& r) {
+        const int gg = b & 3, t = b >> 2, m = t % M, k = (ks0 + t / M) * 128 + gg * 32;
+        const bool on = k < a.K;                                         // K % 32 == 0: whole blocks (the padding of the last k-step is zero)
+        const char* p = (const char*)a.x + ((size_t)m * a.ldx + (on ? k : 0)) * (XF32 ? 4 : 2);
+#pragma unroll
+        for (int j = 0; j < (XF32 ? 8 : 4); ++j) {
+            r.v[j] = *(const std::conditional_t<XF32, f32x4, u32x4>*)(p + j * 16);
+            if (!on) r.v[j] = std::conditional_t<XF32, f32x4, u32x4>{0, 0, 0, 0};
+        }
+    };
+    auto x_quant_store = [&](int b, const XRaw& r) {
+        float v[32];
+        if constexpr (XF32) {
+#pragma unroll
+            for (int j = 0; j < 32; ++j) v[j] = r.v[j >> 2][j & 3];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t d = r.v[j >> 2][j & 3];
+                v[2 * j] = bf2f(d & 0xffff);
+                v[2 * j + 1] = bf2f(d >> 16);
+            }
+        }
+        if constexpr (NORM) {                                            // sm_norm's formula, kept in fp32: gamma * (x * rstd)
+            const int gg = b & 3, t = b >> 2, m = t % M, k = (ks0 + t / M) * 128 + gg * 32;
+            float tot = 0.f;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) tot += nsum[m * WAVES + w];
+            const float rs = rsqrtf(tot / (float)a.K + a.neps);
+            if (k < a.K) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const f32x4 gm = *(const f32x4*)(a.ngamma + k + 4 * j);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[4 * j + e] = gm[e] * (v[4 * j + e] * rs);
+                }
+            }
+        }
+        uint32_t hi[8], lo[8], sc;
+        quant32_hi_lo(v, hi, lo, sc);
+        // e4m3 operand map: block G = b & 3 -- its first 16 k are half G >> 1 of lane group 2 (G & 1), the next 16 the same half of the group after it
+        char* dst = xq + (size_t)(b >> 2) * 256 + (b & 1) * 64 + ((b >> 1) & 1) * 16;
+        *(u32x4*)dst = u32x4{hi[0], hi[1], hi[2], hi[3]};
+        *(u32x4*)(dst + 32) = u32x4{hi[4], hi[5], hi[6], hi[7]};
+        *(u32x4*)(dst + 128) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        *(u32x4*)(dst + 160) = u32x4{lo[4], lo[5], lo[6], lo[7]};
+        xsc[b] = (uint16_t)sc;
+    };
+    if constexpr (NORM) {                                                // row sums of squares first (the launcher keeps K whole: one slice)
+        for (int m = 0; m < M; ++m) {
+            const float* xm = (const float*)a.x + (size_t)m * a.ldx;
+            float sq = 0.f;
+            for (int c = tid; c < (a.K >> 2); c += NT) {
+                const f32x4 q = *(const f32x4*)(xm + (size_t)c * 4);
+                sq += q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+            }
+            sq = wave_sum(sq);
+            if (lane == 0) nsum[m * WAVES + wave] = sq;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    }
+    XRaw xr0;
+    if (tid < nblk) x_load(tid, xr0);                                   // ahead of the weights in the vector-memory queue
+    auto x_phase = [&]() {
+        if (tid < nblk) x_quant_store(tid, xr0);
+        for (int b = tid + NT; b < nblk; b += NT) {
+            XRaw r;
+            x_load(b, r);
+            x_quant_store(b, r);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    };
+
+    // ---- weights: a ring of D quads per wave and matrix
+    struct Quad { u32x4 c[4]; uint32_t s; };
+    const int nq = q1 - q0, nw = wave < nq ? (nq - wave + WAVES - 1) / WAVES : 0;
+    auto issue = [&](int c, Quad& w, Quad& w2) {
+        const int q = q0 + wave + c * WAVES;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int ks = min(4 * q + h, KS - 1);                       // the last quad may be short: re-read, skipped below
+            w.c[h] = __builtin_nontemporal_load((const u32x4*)(wrg + (size_t)ks * 1024) + lane);
+            if (DUAL) w2.c[h] = __builtin_nontemporal_load((const u32x4*)(wrg2 + (size_t)ks * 1024) + lane);
+        }
+        w.s = __builtin_nontemporal_load((const uint32_t*)(wrg + (size_t)KS * 1024 + (size_t)q * 256) + lane);
+        if (DUAL) w2.s = __builtin_nontemporal_load((const uint32_t*)(wrg2 + (size_t)KS * 1024 + (size_t)q * 256) + lane);
+    };
+    f32x4 acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
+    const int mrow = i < M ? i : 0;                // B columns >= M: any finite-or-not data, their D columns are never stored
+    auto consume = [&](const Quad& w, const Quad& w2, int c) {
+        const int q = q0 + wave + c * WAVES;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int ks = 4 * q + h;
+            if (ks < KS) {                                               // wave-uniform
+                const int t = (ks - ks0) * M + mrow;
+                const char* xb = xq + (size_t)t * 256 + g * 32;           // this lane's 16 + 16 k of the row (e4m3 operand map)
+                const u32x4 h0 = *(const u32x4*)xb, h1 = *(const u32x4*)(xb + 16), l0 = *(const u32x4*)(xb + 128), l1 = *(const u32x4*)(xb + 144);
+                const uint32_t sx = xsc[t * 4 + g];
+                const i32x8 bh = {(int)h0[0], (int)h0[1], (int)h0[2], (int)h0[3], (int)h1[0], (int)h1[1], (int)h1[2], (int)h1[3]};
+                const i32x8 bl = {(int)l0[0], (int)l0[1], (int)l0[2], (int)l0[3], (int)l1[0], (int)l1[1], (int)l1[2], (int)l1[3]};
+                const int sxh = (int)(sx & 0xffu), sxl = (int)(sx >> 8);
+                // cbsz 4: A is e2m1 (its first four registers), blgp 0: B is e4m3; scale bytes in byte 0 of the scale operands
+                const i32x8 af = {(int)w.c[h][0], (int)w.c[h][1], (int)w.c[h][2], (int)w.c[h][3], 0, 0, 0, 0};
+                const int sa = (int)((w.s >> (8 * h)) & 0xffu);
+                acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bh, acc, 4, 0, 0, sa, 0, sxh);
+                acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bl, acc, 4, 0, 0, sa, 0, sxl);
+                if (DUAL) {
+                    const i32x8 af2 = {(int)w2.c[h][0], (int)w2.c[h][1], (int)w2.c[h][2], (int)w2.c[h][3], 0, 0, 0, 0};
+                    const int sa2 = (int)((w2.s >> (8 * h)) & 0xffu);
+                    acc2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af2, bh, acc2, 4, 0, 0, sa2, 0, sxh);
+                    acc2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af2, bl, acc2, 4, 0, 0, sa2, 0, sxl);
+                }
+            }
+        }
+    };
+    Quad wq[D], wq2[D];
+    int done = 0, issued, live;
+    if (nw >= 2 * D) {
+        // the ring proper, with a straight-line entry of its own (as skinny_fp8_kernel: predicated issues in front of the loop make
+        // the compiler's wait-count analysis drain the queue at the top of every round)
+#pragma unroll
+        for (int u = 0; u < D; ++u) issue(u, wq[u], wq2[u]);
+        x_phase();
+        issued = live = D;
+        for (; issued + D <= nw; issued += D, done += D) {
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                consume(wq[u], wq2[u], done + u);
+                issue(issued + u, wq[u], wq2[u]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    } else {
+        issued = live = min(nw, D);
+#pragma unroll
+        for (int u = 0; u < D; ++u)
+            if (u < live) issue(u, wq[u], wq2[u]);
+        x_phase();
+    }
+    const int rem = nw - issued;                    // < D quads left: each takes the registers of the quad just consumed
+#pragma unroll
+    for (int u = 0; u < D; ++u)
+        if (u < live) {
+            consume(wq[u], wq2[u], done + u);
+            if (u < rem) issue(issued + u, wq[u], wq2[u]);
+        }
+#pragma unroll
+    for (int u = 0; u < D - 1; ++u)
+        if (u < rem) consume(wq[u], wq2[u], issued + u);
+
+    if (WAVES > 1) {                                // K cut over the waves: partial sums meet in LDS, summed in wave order
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            red[(wave * PER + r) * 64 + lane] = acc[r];
+            if (DUAL) red[(wave * PER + 4 + r) * 64 + lane] = acc2[r];
+        }
+        __syncthreads();
+        if (wave != 0) return;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float s = 0.f, s2 = 0.f;
+            for (int w = 0; w < WAVES; ++w) {
+                s += red[(w * PER + r) * 64 + lane];
+                if (DUAL) s2 += red[(w * PER + 4 + r) * 64 + lane];
+            }
+            acc[r] = s;
+            if (DUAL) acc2[r] = s2;
+        }
+    }
+    // D[n = 4g + r][m = i] (the C / D map of every 16 x 16 MFMA): lane (g, i) owns outputs n0 .. n0 + 3 of row i
+    const int n0 = rg * 16 + g * 4;
+    if (ws) {                                       // K slices: raw partial sums into slab blockIdx.y, [m][N padded to 4]
+        if (i >= M || n0 >= a.N) return;
+        const int ldw = (a.N + 3) & ~3;
+        const size_t o = ((size_t)blockIdx.y * M + i) * ldw + n0;
+        for (int r = 0; r < 4; ++r)
+            if (n0 + r < a.N) { ws[o + r] = acc[r]; if (DUAL) ws2[o + r] = acc2[r]; }
+        return;
+    }
+    store4(a, i, n0, acc, DUAL ? &acc2 : nullptr);
+}
+
+template <int WAVES>
+static int launch_fp4_waves(const LinArgs& a, bool xf32, bool dual, int qps, int S, float* ws, float* ws2, hipStream_t st) {
+    const bool norm = a.ngamma != nullptr;
+    const dim3 grid(a.NRG, S), block(WAVES * 64);
+    const size_t sh = ((size_t)WAVES * (dual ? 8 : 4) * 64 + (norm ? 16 * WAVES : 0)) * sizeof(float) + (size_t)qps * 4 * a.M * FP4_X_BYTES;
+#define F4(XF, DU, NO) skinny_fp4_kernel<WAVES, XF, DU, NO><<<grid, block, sh, st>>>(a, qps, ws, ws2)
+    if (norm) { if (dual) F4(true, true, true); else F4(true, false, true); }
+    else if (xf32) { if (dual) F4(true, true, false); else F4(true, false, false); }
+    else { if (dual) F4(false, true, false); else F4(false, false, false); }
+#undef F4
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+
+// sm_linear with SM_W_FP4 and M <= 16 (linear.hip validated the call)
+int launch_skinny_fp4(const LinArgs& a, bool xf32, hipStream_t st) {
+    const bool dual = a.w2 != nullptr;
+    const int KS = (a.K + 127) / 128, KQ = (KS + 3) / 4;
+    int qps = (44 * 1024) / (FP4_X_BYTES * 4 * a.M);                    // quads of x per block that fit the LDS budget (>= 2 at 16 rows; + 16.5 KiB of sums < 64 KiB)
+    if (qps > KQ) qps = KQ;
+    const int S = (KQ + qps - 1) / qps;
+    qps = (KQ + S - 1) / S;                                             // even slices
+    SM_REQUIRE(!a.ngamma || S == 1, "sm_linear: fp4 weights with fused RMSNorm need the normalised rows in one K slice (M=%d K=%d)", a.M, a.K);
+    float *ws = nullptr, *ws2 = nullptr;
+    if (S > 1) {
+        const size_t slab = (size_t)S * a.M * ((a.N + 3) & ~3);
+        int rc = splitk_workspace(st, slab * sizeof(float) * (dual ? 2 : 1), &ws);
+        if (rc) return rc;
+        if (dual) ws2 = ws + slab;
+    }
+    // waves per block: at least two quads per wave where K allows (a ring needs something to ring)
+    int rc;
+    if (qps >= 16) rc = launch_fp4_waves<8>(a, xf32, dual, qps, S, ws, ws2, st);
+    else if (qps >= 4) rc = launch_fp4_waves<4>(a, xf32, dual, qps, S, ws, ws2, st);
+    else rc = launch_fp4_waves<1>(a, xf32, dual, qps, S, ws, ws2, st);
+    if (rc || S == 1) return rc;
+    return launch_splitk_reduce(a, ws, S, (a.N + 3) & ~3, st, ws2);
+}

@@ -1191,14 +1191,14 @@ int sm_linear_reserve(hipStream_t st, size_t slab_bytes, size_t dual_bytes) {
     if (!rc && dual_bytes) rc = dual_workspace(st, dual_bytes, &p);
     return rc;
 }
-int launch_splitk_reduce(const LinArgs& a, const float* ws, int S, int ldw, hipStream_t st) {
+int launch_splitk_reduce(const LinArgs& a, const float* ws, int S, int ldw, hipStream_t st, const float* ws2) {
     const size_t nthr = (size_t)a.M * ((a.N + 3) / 4);
-    splitk_reduce_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, st>>>(a, ws, nullptr, S, ldw);
+    splitk_reduce_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, st>>>(a, ws, ws2, S, ldw);
     SM_LAUNCH_CHECK();
     return SM_OK;
 }
 
-// bf16 expansion of fp8 weights for M > 16 (per HIP stream, grown on demand; slot 0 = w, slot 1 = w2)
+// bf16 expansion of fp8 / fp4 weights for M > 16 (per HIP stream, grown on demand; slot 0 = w, slot 1 = w2)
 static std::map<hipStream_t, std::pair<void*, size_t>> g_dq[2];
 void release_fp8_workspace(hipStream_t st);                                 // gemm_fp8.hip
 // a HIP stream this library created is about to be destroyed (already synchronised): drop the slabs keyed on it
@@ -1216,20 +1216,29 @@ void release_stream_workspaces(hipStream_t st) {
     }
     release_fp8_workspace(st);
 }
+static int dequant_workspace(hipStream_t st, int which, size_t bytes, void** out) {
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    auto& e = g_dq[which][st];
+    if (e.second < bytes) {
+        if (e.first) { SM_HIP(hipStreamSynchronize(st)); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
+        SM_HIP(hipMalloc(&e.first, bytes));
+        e.second = bytes;
+    }
+    *out = e.first;
+    return SM_OK;
+}
+static int dequant_fp4(hipStream_t st, int which, const void* w4, int N, int K, const void** out) {
+    void* dst;
+    int rc = dequant_workspace(st, which, sm_packed_elems(N, K) * 2, &dst);
+    if (rc) return rc;
+    *out = dst;
+    return launch_dequant_fp4(w4, N, K, dst, st);
+}
 static int dequant_fp8(hipStream_t st, int which, const void* w8, const float* scale, int N, int K, const void** out) {
     const int KS = (K + 31) / 32, KSP = (KS + 1) / 2, NRG = (N + 15) / 16;
     const size_t bytes = (size_t)NRG * KS * 1024;
     void* dst;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto& e = g_dq[which][st];
-        if (e.second < bytes) {
-            if (e.first) { SM_HIP(hipStreamSynchronize(st)); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
-            SM_HIP(hipMalloc(&e.first, bytes));
-            e.second = bytes;
-        }
-        dst = e.first;
-    }
+    {   int rc = dequant_workspace(st, which, bytes, &dst); if (rc) return rc; }
     const size_t chunks = (size_t)NRG * KSP * 64;
     dequant_fp8_kernel<<<(unsigned)((chunks + 255) / 256), 256, 0, st>>>((const u32x4*)w8, scale, N, KS, KSP, (u32x4*)dst, chunks);
     SM_LAUNCH_CHECK();
@@ -1530,7 +1539,7 @@ int sm_linear_qkv_rope(const sm_linear_t* p, const SmRopeEpi& re, void* stream) 
     LinArgs a;
     fill_args(p, a);
     hipStream_t st = (hipStream_t)stream;
-    SmProfScope prof(SM_PROF_SKINNY, st);
+    SmProfScope prof(SM_PROF_SKINNY, st, ((long long)p->N << 32) | (unsigned)p->K);
     constexpr int WAVES = 8;
     SM_REQUIRE(a.KS >= WAVES * 4, "sm_linear_qkv_rope: K too small");
     const dim3 grid((re.H + 2 * re.KV) * 4), block(WAVES * 64);
@@ -1753,6 +1762,26 @@ static int linear_impl(const sm_linear_t* p, void* stream, bool* ln_done) {
     SM_REQUIRE(!p->vt || (p->vt_dh > 0 && p->vt_S > 0 && (p->N - p->vt_n0) % p->vt_dh == 0), "sm_linear: bad vt args");
     hipStream_t st = (hipStream_t)stream;
     const bool xf32 = p->x_dtype == SM_X_F32;
+    if (p->w_dtype == SM_W_FP4) {
+        // MXFP4 weights (gemm_fp4.hip).  Up to 16 rows: the block-scaled MFMA weight stream; what that kernel does not do is refused, never
+        // replaced by a different product.  More rows: the image is expanded to a packed bf16 scratch and the bf16 kernels below run on it.
+        SM_REQUIRE(p->op_dtype == SM_OP_BF16, "sm_linear: fp4 weights take bf16 operands (op_dtype SM_OP_F16 is not supported)");
+        SM_REQUIRE(!p->vt && p->remap_in == 0 && p->x_rep <= 1, "sm_linear: fp4 weights: plain rows only (no vt / remap / x_rep)");
+        if (p->M <= 16) {
+            SM_REQUIRE(!p->precise, "sm_linear: fp4 weights: `precise` is not supported (the activations already enter as an e4m3 hi + lo pair)");
+            SM_REQUIRE(!p->post_ln_gamma, "sm_linear: fp4 weights: post_ln_* is not supported up to 16 rows (run sm_norm behind the call)");
+            SM_REQUIRE((p->K & 31) == 0 && p->ldx >= p->K && (p->ldx % (xf32 ? 4 : 8)) == 0 && ((uintptr_t)p->x & 15) == 0,
+                       "sm_linear: fp4 weights need K %% 32 == 0 and 16-byte aligned x rows (K=%d ldx=%d)", p->K, p->ldx);
+            SmProfScope prof(SM_PROF_SKINNY, st, ((long long)p->N << 32) | (unsigned)p->K);
+            return launch_skinny_fp4(a, xf32, st);
+        }
+        const void *d0 = nullptr, *d1 = nullptr;
+        int rc = dequant_fp4(st, 0, p->w, p->N, p->K, &d0);
+        if (!rc && p->w2) rc = dequant_fp4(st, 1, p->w2, p->N, p->K, &d1);
+        if (rc) return rc;
+        a.w = (const bf16x8*)d0;
+        if (p->w2) a.w2 = (const bf16x8*)d1;
+    }
     if (p->w_dtype == SM_W_FP8_MFMA && p->M > 16 && (p->K & 127) == 0 && (p->ldx & 7) == 0 && !p->precise && !p->w2 && !xf32 && !p->vt && p->remap_in == 0) {
         // fp8 x fp8 on the matrix pipe: activation rows quantised to e4m3, no bf16 expansion of the weights (gemm_fp8.hip)
         SmProfScope prof(SM_PROF_GEMM, st, ((long long)p->N << 32) | (unsigned)p->K);
@@ -1785,7 +1814,7 @@ static int linear_impl(const sm_linear_t* p, void* stream, bool* ln_done) {
         SM_REQUIRE(xf32 || (p->ldx % 8 == 0), "sm_linear: bf16 x needs ldx %% 8 == 0");
         const bool split = xf32 && p->precise;
         const bool dual = p->w2 != nullptr;
-        SmProfScope prof(SM_PROF_SKINNY, st);
+        SmProfScope prof(SM_PROF_SKINNY, st, ((long long)p->N << 32) | (unsigned)p->K);       // (tag: per-shape times, tools/decode_bench.py --fp4)
         if (p->norm_gamma) {
             // the dual (gate / up) kernel as 4-wave blocks: 896 blocks of 8 waves are 1.75 rounds of the 512 block slots of the chip,
             // smaller blocks leave a shorter tail (Mistral-7B decode 343.5 -> 346.8 tokens/s, fp8 519 -> 524); the single-matrix

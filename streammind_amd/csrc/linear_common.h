@@ -138,5 +138,7 @@ int launch_gemm256(const LinArgs& a, int act, int bn, hipStream_t st, int S = 1)
 int launch_wstream(const LinArgs& a, hipStream_t st, float* ws, int S, int ksl);      // wstream.hip (33..128 rows: weights straight into register rings, X through LDS by a loader wave)
 int launch_gemm_fp8(LinArgs& a, hipStream_t st);                            // gemm_fp8.hip (fp8 x fp8 MFMA, activations quantised per row)
 int splitk_workspace(hipStream_t st, size_t bytes, float** out);            // linear.hip: per-HIP-stream fp32 slabs of the split-K kernels
-int launch_splitk_reduce(const LinArgs& a, const float* ws, int S, int ldw, hipStream_t st);     // ... their fixed-order sum + the real epilogue
+int launch_splitk_reduce(const LinArgs& a, const float* ws, int S, int ldw, hipStream_t st, const float* ws2 = nullptr);     // ... their fixed-order sum + the real epilogue (ws2: the dual image's slabs)
+int launch_skinny_fp4(const LinArgs& a, bool xf32, hipStream_t st);          // gemm_fp4.hip (MXFP4 weights, <= 16 rows: block-scaled MFMA, x requantised to e4m3 hi + lo)
+int launch_dequant_fp4(const void* w4, int N, int K, void* dst_packed_bf16, hipStream_t st);     // gemm_fp4.hip (fp4 image -> packed bf16 image, for more rows)
 void release_stream_workspaces(hipStream_t st);                             // linear.hip: free the per-stream slabs of a stream about to be destroyed

@@ -20,6 +20,8 @@ int sm_pack_weight_ks(const void* w, int N, int K, int ldw, int KS, void* out, v
 void release_stream_workspaces(hipStream_t st);                                                 // linear.hip
 extern "C" size_t sm_packed_fp8_bytes(int N, int K);
 extern "C" int sm_quant_pack_weight_fp8(const void* w, int N, int K, int ldw, void* out, float* scale_out, void* stream);
+extern "C" size_t sm_packed_fp4_bytes(int N, int K);
+extern "C" int sm_quant_pack_weight_fp4(const void* w, int N, int K, int ldw, void* out, void* stream);
 
 // ------------------------------------------------------------------------------------------------ small kernels
 __global__ void bf16_to_f32_kernel(const bf16_t* in, float* out, size_t n) {
@@ -123,6 +125,7 @@ struct Slot {            // one tensor the path reads
     bool complete() const { return loaded == (parts >= 32 ? 0xffffffffu : (1u << parts) - 1u); }
     int Klogical = 0;    // > 0: checkpoint K (the packed image pads it to K); patch embedding only
     bool fp8 = false;    // packed as fp8 + per-row scales (weights_fp8 mode, gate + LLM linears)
+    bool fp4 = false;    // packed as MXFP4, scale bytes inside the image (sm_model_set_weights_fp4: the LLM's q|k|v, o, gate|up, down)
     bool wo = false;     // fp8 slot that is weight-only in EVERY fp8 mode (the gate: its rows are never quantised, so a pass of 17..32 rows streams the fp8 image)
     bool f16 = false;    // packed image holds IEEE fp16 instead of bf16 (vit_fp16 mode, ViT linears)
     DevBuf scale;        // fp32 [N]
@@ -130,6 +133,8 @@ struct Slot {            // one tensor the path reads
 
 struct sm_model {
     sm_config_t c;
+    bool weights_fp4 = false;      // sm_model_set_weights_fp4 (not part of sm_config_t: the struct is ABI)
+    bool any_loaded = false;       // a tensor has been handed over: the weight formats are fixed from here on
     std::unordered_map<std::string, Slot> slots;           // canonical name -> storage
     struct Route { std::string slot; int row0; int rows; int part; };   // checkpoint name -> (slot, first row, row count, index of this part)
     std::unordered_map<std::string, Route> routes;
@@ -426,6 +431,7 @@ extern "C" int sm_model_load_tensor(sm_model* m, const char* name_c, const void*
         SM_FAIL(SM_EINVAL, "sm_model_load_tensor: unknown tensor '%s' (canonical '%s')", name_c, name.c_str());
     }
     Slot& s = m->slots[it->second.slot];
+    m->any_loaded = true;
     const int row0 = it->second.row0;
     int64_t rows = shape[0], cols = 1;
     for (int i = 1; i < ndim; ++i) cols *= shape[i];
@@ -452,7 +458,13 @@ extern "C" int sm_model_load_tensor(sm_model* m, const char* name_c, const void*
             else f16_to_bf16_kernel<<<nb, 256, 0, st>>>((const _Float16*)data, tmp.as<bf16_t>(), n);
             src = tmp.as<bf16_t>();
         }
-        if (s.kind == 1 && s.fp8) {
+        if (s.kind == 1 && s.fp4) {
+            if (!s.buf.p) { int rc = s.buf.alloc(sm_packed_fp4_bytes(s.N, s.K), true); if (rc) return rc; }
+            SM_REQUIRE(row0 % 16 == 0, "fused part must start on a 16-row boundary");
+            char* dst = (char*)s.buf.p + (size_t)(row0 / 16) * fp4_rg_bytes((s.K + 127) / 128);
+            int rc = sm_quant_pack_weight_fp4(src, (int)rows, s.K, (int)cols, dst, stream);
+            if (rc) return rc;
+        } else if (s.kind == 1 && s.fp8) {
             if (!s.buf.p) {
                 int rc = s.buf.alloc(sm_packed_fp8_bytes(s.N, s.K), true); if (rc) return rc;
                 rc = s.scale.alloc((size_t)s.N * 4, true); if (rc) return rc;
@@ -588,12 +600,35 @@ extern "C" int sm_model_set_fp8_mode(sm_model* m, int mode) {
     m->c.weights_fp8 = mode;
     return SM_OK;
 }
+// MXFP4 weights for the LLM's q|k|v, o, gate|up and down projections (lm_head, the embedding table, the gate, the connector and the tower keep
+// their formats).  Between sm_model_create and the first sm_model_load_tensor: the slots are quantised as they are loaded.
+extern "C" int sm_model_set_weights_fp4(sm_model* m, int on) {
+    SM_REQUIRE(m && !m->any_loaded && !m->finalized, "sm_model_set_weights_fp4: call it between sm_model_create and the first sm_model_load_tensor");
+    SM_REQUIRE(!on || (!m->c.weights_fp8 && !m->c.llm_fp16), "sm_model_set_weights_fp4: exclusive with weights_fp8 and llm_fp16");
+    SM_REQUIRE(!on || m->c.llm_layers == 0 || ((m->c.llm_hidden & 31) == 0 && (m->c.llm_mlp & 31) == 0), "sm_model_set_weights_fp4: llm_hidden and llm_mlp must be multiples of 32");
+    m->weights_fp4 = on != 0;
+    for (auto& kv : m->slots)
+        if (kv.second.kind == 1 && kv.first.rfind("llm.model.layers.", 0) == 0) kv.second.fp4 = m->weights_fp4;
+    return SM_OK;
+}
+extern "C" int sm_norm_ex(const float* x, int M, int D, int ldx, const float* gamma, const float* beta, float eps, int post_act,
+                          float* out_f32, void* out_bf16, int ldo, int op_dtype, void* stream);
+// sm_linear; where the product's kernel does not carry the norm of the finished rows (fp4 weights up to 16 rows) the norm is the launch behind it
+static int linear_post_norm(const sm_linear_t& a, void* stream) {
+    if (a.w_dtype != SM_W_FP4 || a.M > 16 || !a.post_ln_gamma) return sm_linear(&a, stream);
+    sm_linear_t b = a;
+    b.post_ln_gamma = nullptr; b.post_ln_out = nullptr; b.post_ln_out_f32 = nullptr;
+    const int rc = sm_linear(&b, stream);
+    if (rc) return rc;
+    return sm_norm_ex(a.out_f32, a.M, a.N, a.ldo, a.post_ln_gamma, a.post_ln_beta, a.post_ln_eps, a.post_ln_act, a.post_ln_out_f32, a.post_ln_out, a.post_ln_ldo, a.op_dtype, stream);
+}
 
 // ------------------------------------------------------------------------------------------------ ViT
 static sm_linear_t lin(const sm_model* m, const Slot& w, const void* x, int x_dtype, int M, int ldx) {
     sm_linear_t a;
     memset(&a, 0, sizeof(a));
     a.w = w.buf.p; a.N = w.N; a.K = w.K; a.x = x; a.x_dtype = x_dtype; a.M = M; a.ldx = ldx;
+    if (w.fp4) a.w_dtype = SM_W_FP4;
     if (w.fp8) { a.w_dtype = m->c.weights_fp8 == 2 && !w.wo ? SM_W_FP8_MFMA : SM_W_FP8; a.w_scale = w.scale.as<float>(); }
     if (w.f16) a.op_dtype = SM_OP_F16;
     return a;
@@ -1383,7 +1418,8 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
         // call of its own.
         if (!fuse_norm && l == 0 && (rc = sm_norm_ex(x, n, ld, ld, w.ln1_w, nullptr, c.llm_eps, 0, nullptr, W->xnb.p, ld, od, stream))) return rc;
         // decode: RoPE + KV append ride in the epilogue of the q/k/v product (no fp32 q/k/v round trip, one launch less per layer)
-        const bool fuse_rope = fuse_norm && dh == 128 && ld >= 1024 && !g_no_fused_rope;
+        // (fp4 weights: the plain q|k|v product and the RoPE / append launch)
+        const bool fuse_rope = fuse_norm && dh == 128 && ld >= 1024 && !g_no_fused_rope && !w.qkv->fp4;
         {   sm_linear_t a = fuse_norm ? lin(m, *w.qkv, x, SM_X_F32, n, ld) : lin(m, *w.qkv, W->xnb.p, SM_X_BF16, n, ld);
             if (fuse_norm) { a.norm_gamma = w.ln1_w; a.norm_eps = c.llm_eps; }
             if (fuse_rope) {
@@ -1404,13 +1440,14 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
         {   sm_linear_t a = lin(m, *w.o, W->ctxb.p, SM_X_BF16, n, qn);
             a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
             if (!fuse_norm) { a.post_ln_gamma = w.ln2_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = W->xnb.p; a.post_ln_ldo = ld; }
-            if ((rc = sm_linear(&a, stream))) return rc; }
+            if ((rc = linear_post_norm(a, stream))) return rc; }
         if (n <= (c.weights_fp8 == 2 ? 16 : 32)) {   // decode / tiny chunks: SwiGLU fused into the dual weight-streaming kernel (fp8 MFMA mode: above 16 rows the tiled fp8 product)
             const Slot& gu = *w.gu;
             sm_linear_t a = fuse_norm ? lin(m, gu, x, SM_X_F32, n, ld) : lin(m, gu, W->xnb.p, SM_X_BF16, n, ld);
             if (fuse_norm) { a.norm_gamma = w.ln2_w; a.norm_eps = c.llm_eps; }
             a.N = c.llm_mlp;
-            if (gu.fp8) { a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * ((ld / 32 + 1) / 2) * 1024; a.w2_scale = gu.scale.as<float>() + c.llm_mlp; }
+            if (gu.fp4) a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * fp4_rg_bytes((ld + 127) / 128);
+            else if (gu.fp8) { a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * ((ld / 32 + 1) / 2) * 1024; a.w2_scale = gu.scale.as<float>() + c.llm_mlp; }
             else a.w2 = gu.buf.as<bf16_t>() + (size_t)(c.llm_mlp / 16) * (ld / 32) * 512;
             a.out_bf16 = W->actb.p; a.ldo_bf16 = c.llm_mlp;
             if ((rc = sm_linear(&a, stream))) return rc;
@@ -1426,7 +1463,7 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
         {   sm_linear_t a = lin(m, *w.down, W->actb.p, SM_X_BF16, n, c.llm_mlp);
             a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
             if (!fuse_norm && l + 1 < c.llm_layers) { a.post_ln_gamma = m->R.llm[l + 1].ln1_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = W->xnb.p; a.post_ln_ldo = ld; }
-            if ((rc = sm_linear(&a, stream))) return rc; }
+            if ((rc = linear_post_norm(a, stream))) return rc; }
     }
     s->kv_len += n;
     return SM_OK;
@@ -1553,7 +1590,8 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
     // linears on the tiled MFMA GEMM (M = streams) -- still ONE pass over the weights per step -- and the per-stream kernels (token gather,
     // RoPE + KV append, attention, arg-max: per-stream pointers travel by value, SM_MAX_SEG at a time) in chunks
     // (fp8 weights: the weight-streaming kernels read the fp8 image up to 64 rows; beyond that a product would expand it to bf16 per call)
-    const int s_cap = c.weights_fp8 == 2 ? 16 : c.weights_fp8 ? (sm_skinny_lds64_on() ? 64 : SM_MAX_SEG) : SM_GROUP_DECODE_MAX;
+    // (fp4 weights: one pass of the block-scaled weight stream, up to 16 rows)
+    const int s_cap = m->weights_fp4 ? 16 : c.weights_fp8 == 2 ? 16 : c.weights_fp8 ? (sm_skinny_lds64_on() ? 64 : SM_MAX_SEG) : SM_GROUP_DECODE_MAX;
     SM_REQUIRE(S <= s_cap, "sm_group_llm_decode: %d active streams exceed one weight pass (%d)", S, s_cap);
     const int ld = c.llm_hidden, H = c.llm_heads, KV = c.llm_kv_heads, dh = ld / H, qn = H * dh, kn = KV * dh, V = c.llm_vocab;
     // the per-stream kernels of a step take ONE cache pitch (V^T row stride) for all their streams: the active streams are brought to a common capacity --
@@ -1652,7 +1690,7 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
         // up to 8 active streams: RoPE + KV append ride in the epilogue of the q/k/v product, every row against ITS stream's cache and position (the per-row
         // form of the kernel a stream's own decode step uses: one launch and the fp32 q/k/v round trip less per layer); its activations are fp32 rows, so the
         // norm in front of it leaves fp32.  Worth 0.4-1 % on bf16 weights and 2-3 % on fp8 weights at 2..8 streams (same box), nothing at 12.
-        const bool fuse_rope = S <= 8 && dh == 128 && ld >= 1024 && (ld & 31) == 0 && !g_no_fused_rope;
+        const bool fuse_rope = S <= 8 && dh == 128 && ld >= 1024 && (ld & 31) == 0 && !g_no_fused_rope && !m->weights_fp4;
         if (!fuse_norm && c.llm_layers > 0 &&
             (rc = sm_norm_ex(x, S, ld, ld, m->R.llm[0].ln1_w, nullptr, c.llm_eps, 0, fuse_rope ? g->d_xn32.as<float>() : nullptr, fuse_rope ? nullptr : g->d_xnb.p, ld, od, stream))) return rc;
         for (int l = 0; l < c.llm_layers; ++l) {
@@ -1708,13 +1746,14 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
             {   sm_linear_t a = lin(m, *w.o, g->d_ctxb.p, SM_X_BF16, S, qn);
                 a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
                 if (!fuse_norm) { a.post_ln_gamma = w.ln2_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = g->d_xnb.p; a.post_ln_ldo = ld; }
-                if ((rc = sm_linear(&a, stream))) return rc; }
+                if ((rc = linear_post_norm(a, stream))) return rc; }
             if (S <= SM_MAX_SEG || (S <= 64 && (sm_skinny_lds64_on() >= 2 || (sm_skinny_lds64_on() == 1 && c.weights_fp8)))) {
                 const Slot& gu = *w.gu;
                 sm_linear_t a = fuse_norm ? lin(m, gu, x, SM_X_F32, S, ld) : lin(m, gu, g->d_xnb.p, SM_X_BF16, S, ld);
                 if (fuse_norm) { a.norm_gamma = w.ln2_w; a.norm_eps = c.llm_eps; }
                 a.N = c.llm_mlp;
-                if (gu.fp8) { a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * ((ld / 32 + 1) / 2) * 1024; a.w2_scale = gu.scale.as<float>() + c.llm_mlp; }
+                if (gu.fp4) a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * fp4_rg_bytes((ld + 127) / 128);
+                else if (gu.fp8) { a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * ((ld / 32 + 1) / 2) * 1024; a.w2_scale = gu.scale.as<float>() + c.llm_mlp; }
                 else a.w2 = gu.buf.as<bf16_t>() + (size_t)(c.llm_mlp / 16) * (ld / 32) * 512;
                 a.out_bf16 = g->d_actb.p; a.ldo_bf16 = c.llm_mlp;
                 if ((rc = sm_linear(&a, stream))) return rc;
@@ -1733,7 +1772,7 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
                     if (fuse_rope && l + 1 < c.llm_layers) a.post_ln_out_f32 = g->d_xn32.as<float>();     // (the fused q/k/v + RoPE product reads fp32 rows)
                     else a.post_ln_out = g->d_xnb.p;
                 }
-                if ((rc = sm_linear(&a, stream))) return rc; }
+                if ((rc = linear_post_norm(a, stream))) return rc; }
         }
         for (sm_stream* s : act) s->kv_len += 1;
         if (!fuse_norm && c.llm_layers == 0 && (rc = sm_norm_ex(x, S, ld, ld, m->R.llm_norm, nullptr, c.llm_eps, 0, nullptr, g->d_xnb.p, ld, od, stream))) return rc;

@@ -60,6 +60,7 @@ class PathConfig:
     gate_precise: bool = True
     weights_fp8: int = 0           # opt-in BASELINE config 5: 1 = fp8 gate + LLM weights (weight-only: bf16 activations); 2 = the same,
                                    # and calls with > 16 rows run fp8 x fp8 MFMA on per-row-quantised activations (gemm_fp8.hip)
+    weights_fp4: bool = False      # opt-in: the LLM's q|k|v, o, gate|up, down as MXFP4 images (sm_model_set_weights_fp4; exclusive with weights_fp8 / llm_fp16)
     vit_fp16: bool = False         # vision-tower operands in IEEE fp16 (the reference demo's precision) instead of bf16
     llm_fp16: bool = False         # the same for the LLM (weights, embedding table, activations, q / KV caches, attention P)
     proj_fp16: bool = False        # the same for the connector + gate weights (activations as fp16 hi/lo pairs in precise mode)
@@ -116,6 +117,8 @@ class NativeModel:
         ccfg = cfg.to_c()
         check(self.lib.sm_model_create(C.byref(ccfg), C.byref(h)), "sm_model_create")
         self.h = h
+        if getattr(cfg, "weights_fp4", False):       # not a field of sm_config_t (the struct is ABI): a setter, before the first tensor
+            check(self.lib.sm_model_set_weights_fp4(self.h, 1), "sm_model_set_weights_fp4")
         self.finalized = False
         self.ignored = []
 
@@ -413,6 +416,25 @@ def pack_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return out, scale
 
 
+def pack_weight_fp4(w: torch.Tensor) -> torch.Tensor:
+    """[N,K] bf16 (GPU) -> the MXFP4 image (uint8: e2m1 codes and the e8m0 scale bytes of every 32-block, sm_quant_pack_weight_fp4)."""
+    lib = _lib.load()
+    assert w.dtype == torch.bfloat16 and w.is_cuda and w.dim() == 2 and w.is_contiguous()
+    N, K = w.shape
+    out = torch.empty(lib.sm_packed_fp4_bytes(N, K), dtype=torch.uint8, device=w.device)
+    check(lib.sm_quant_pack_weight_fp4(w.data_ptr(), N, K, K, out.data_ptr(), _stream()), "sm_quant_pack_weight_fp4")
+    return out
+
+
+def unpack_weight_fp4(wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """MXFP4 image -> the values it stands for, bf16 [N,K] (code x 2^(e - 127), exact in bf16)."""
+    lib = _lib.load()
+    assert wp.dtype == torch.uint8 and wp.is_cuda and wp.is_contiguous() and wp.numel() == lib.sm_packed_fp4_bytes(N, K)
+    out = torch.empty(N, K, dtype=torch.bfloat16, device=wp.device)
+    check(lib.sm_unpack_weight_fp4(wp.data_ptr(), N, K, out.data_ptr(), K, _stream()), "sm_unpack_weight_fp4")
+    return out
+
+
 def ingest_frames(frames: torch.Tensor, pad_square: bool = True, image_size: int = 336,
                   pad_rgb: Sequence[int] = (122, 116, 104)) -> torch.Tensor:
     """f2: u8 frames [n, H, W, 3] of any size on the GPU -> u8 [n, image_size, image_size, 3]: optional expand2square with
@@ -501,14 +523,15 @@ def linear(x: torch.Tensor, wp: torch.Tensor, N: int, K: int, *, w2p: Optional[t
            out: Optional[torch.Tensor] = None, fp8_mfma: bool = False, out16: Optional[torch.Tensor] = None,
            post_ln: Optional[Tuple[torch.Tensor, Optional[torch.Tensor], float, torch.Tensor]] = None, post_ln_act: int = 0,
            x_rep: Optional[Tuple[int, int]] = None, fold_out: Optional[torch.Tensor] = None,
-           fold_in: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float]] = None) -> torch.Tensor:
+           fold_in: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float]] = None, w_fp4: bool = False) -> torch.Tensor:
     """Operator-level entry used by the parity tests: y = epilogue(x @ W^T); norm_gamma: RMSNorm of x fused in front.
     LayerNorm folding (sm_linear_t.fold_*): fold_out = stats [M, N / 256, 2] fp32 turns a post_ln call into the PRODUCER (post_ln's `out` receives
     16-bit(y * gamma), stats the per-tile row sums); fold_in = (stats [M, K / 256, 2], g [N], c [N], eps) makes the call the CONSUMER of such rows.
     post_ln = (gamma, beta | None, eps, out [M, N]): LayerNorm (beta given) / RMSNorm of the finished fp32 rows into `out` (16-bit or fp32) from
     the same call (sm_linear_t.post_ln_*), post_ln_act applied to the normalised value; x_rep = (rep, dh): x holds K / rep columns and column
     group j of width dh is read rep times (the gate's repeat_kv in front of o_proj).
-    fp8_mfma (with w_scale): SM_W_FP8_MFMA -- above 16 rows the activations are quantised per row and the product is fp8 x fp8."""
+    fp8_mfma (with w_scale): SM_W_FP8_MFMA -- above 16 rows the activations are quantised per row and the product is fp8 x fp8.
+    w_fp4: wp (and w2p) are MXFP4 images (pack_weight_fp4): SM_W_FP4."""
     lib = _lib.load()
     assert x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.dtype in (torch.bfloat16, torch.float32, torch.float16)
     if x.dtype == torch.float16:       # fp16 operands: `wp` must be the packed image of fp16 weights (pack_weight moves 16-bit words)
@@ -528,6 +551,9 @@ def linear(x: torch.Tensor, wp: torch.Tensor, N: int, K: int, *, w2p: Optional[t
     a.bias, a.act = _p(bias), act
     if w_scale is not None:
         a.w_dtype, a.w_scale, a.w2_scale = (_lib.SM_W_FP8_MFMA if fp8_mfma else _lib.SM_W_FP8), w_scale.data_ptr(), _p(w2_scale)
+    if w_fp4:
+        assert w_scale is None, "an MXFP4 image carries its scales"
+        a.w_dtype = _lib.SM_W_FP4
     if residual is not None:
         a.residual, a.ldr = residual.data_ptr(), residual.shape[1]
     if norm_gamma is not None:

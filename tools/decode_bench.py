@@ -1,9 +1,61 @@
-"""Mistral-7B decode-only micro-benchmark (for rocprofv3 kernel traces of the decode step)."""
-import os, sys, time
+"""Mistral-7B decode-only micro-benchmark (for rocprofv3 kernel traces of the decode step).
+--fp4 [n_new]: batch-1 decode on bf16, fp8 and MXFP4 weights in ONE run on one box, the formats alternating over three rounds: tokens/s (median), the
+fraction of the HBM roof on each format's own bytes per token, the summed HIP-event time of the weight-streaming launches per token, the same per
+product shape (us per launch, TB/s on the product's own weight bytes), and ms per batched decode step at 4 / 8 / 16 streams."""
+import ctypes as C
+import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from streammind_amd.native import NativeModel, PathConfig
+
+
+def three_formats(n_new):
+    d, legs = 4096, {}
+    for name, kw in (("bf16", {}), ("fp8", dict(weights_fp8=1)), ("fp4", dict(weights_fp4=True))):
+        cfg = PathConfig(llm_layers=32, max_frames_per_call=1, vit_layers=2, **kw)
+        m = NativeModel(cfg)
+        bench.random_weights_into(m, cfg, 1)
+        bench.random_llm_weights_into(m, cfg, 2)
+        m.finalize()
+        legs[name] = (cfg, m, m.open_stream(max_frames=1024, max_seq=1024))
+    lin = 32 * (d * d * 2 + 2 * d * 1024 + 3 * d * 14336)                      # weights of the LLM's linears
+    wbytes = {"bf16": 2.0 * lin, "fp8": 1.0 * lin + 4 * 32 * (6144 + 4096 + 28672 + 4096), "fp4": lin * (0.5 + 1 / 32)}
+    tps = {k: [] for k in legs}
+    for _ in range(3):                                                          # alternate: a drifting box hits every format alike
+        for name, (cfg, m, s) in legs.items():
+            tps[name].append(bench.decode_leg(m, s, cfg, n_new=n_new)["tokens_per_s"])
+    out = {}
+    for name, (cfg, m, s) in legs.items():
+        t = statistics.median(tps[name])
+        r = bench.decode_leg(m, s, cfg, n_new=16)["roofline"]
+        rest = r["bytes_per_token"] - 2.0 * lin                                 # lm_head (bf16 in every format) + the K / V caches
+        byts = wbytes[name] + rest
+        lib = m.lib
+        lib.sm_prof_reset(); lib.sm_prof_enable(1 << 1)                         # class 1: the weight-streaming launches
+        s.decode(32); torch.cuda.synchronize()
+        lib.sm_prof_enable(0)
+        cnt, ms = C.c_int(), C.c_float()
+        lib.sm_prof_read(1, C.byref(cnt), C.byref(ms))
+        shapes = {}                                                             # per product of a layer: HIP-event us per launch, and TB/s on its own weight bytes
+        bpw = {"bf16": 2.0, "fp8": 1.0, "fp4": 0.5 + 1 / 32}[name]
+        for label, N, K, mats in (("qkv", 6144, 4096, 1), ("o", 4096, 4096, 1), ("gate_up", 14336, 4096, 2), ("down", 4096, 14336, 1), ("lm_head", cfg.llm_vocab, 4096, 1)):
+            c2, m2 = C.c_int(), C.c_float()
+            lib.sm_prof_read_tag(1, C.c_longlong((N << 32) | K), C.byref(c2), C.byref(m2))
+            if c2.value:
+                us = m2.value * 1e3 / c2.value
+                shapes[label] = {"launches": c2.value, "us": round(us, 2), "tb_s": round(mats * N * K * (bpw if label != "lm_head" or name == "fp8" else 2.0) / us / 1e6, 2)}
+        grp = bench.group_decode_leg(m, cfg, sizes=(4, 8, 16), n_new=48)       # batched decode, up to the 16 rows one fp4 weight pass takes
+        shapes["group_decode_ms_per_step"] = dict(zip(grp["streams"], grp["ms_per_step"]))
+        out[name] = {"per_shape": shapes, "tokens_per_s": round(t, 1), "runs": tps[name], "bytes_per_token": byts, "hbm_frac": round(byts * t / 1e9 / bench.HBM_PEAK_GBS, 4),
+                     "weight_stream_ms_per_token": round(ms.value / 32, 4), "weight_stream_launches_per_token": cnt.value // 32, "ms_per_token": round(1e3 / t, 4)}
+    print(json.dumps({"decode_three_formats": out}))
+
+
+if "--fp4" in sys.argv:
+    i = sys.argv.index("--fp4")
+    three_formats(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 128)
+    sys.exit(0)
 
 cfg = PathConfig(llm_layers=32, max_frames_per_call=1, vit_layers=2, weights_fp8=os.environ.get("FP8", "0") == "1", llm_fp16=os.environ.get("FP16", "0") == "1")    # short ViT: perception is not measured here; FP8=1: weight-only fp8 mode; FP16=1: fp16 operands (llm_fp16)
 model = NativeModel(cfg)
