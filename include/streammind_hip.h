@@ -42,6 +42,8 @@ extern "C" {
 #define SM_W_FP8 1
 #define SM_W_FP8_MFMA 2   /* the SM_W_FP8 image; calls with > 16 rows quantise the activations per row to e4m3 and run fp8 x fp8 MFMA */
 #define SM_W_FP4 3        /* the sm_quant_pack_weight_fp4 image (OCP MXFP4: e2m1 codes + one e8m0 scale per 32 k, scales inside the image) */
+#define SM_W_FP4_MFMA 4   /* the SM_W_FP4 image; calls with 17..128 rows quantise the activations once (e4m3 hi + lo per 32-block) and stream the codes
+                           * through the block-scaled MFMA (gemm_fp4.hip, "17..128 rows"); <= 16 rows and > 128 rows are SM_W_FP4 */
 #define SM_OP_BF16 0  /* 16-bit operands (packed weights, x, 16-bit outputs) are bfloat16 */
 #define SM_OP_F16 1   /* ... IEEE half: tiled GEMM only (the ViT's optional fp16 mode = the reference demo's precision, builder.py:54) */
 #define SM_TILE_AUTO 0
@@ -78,7 +80,11 @@ int sm_quant_pack_weight_fp8(const void* w_bf16, int N, int K, int ldw, void* ou
  * mode is weight-only in effect); bias, act, fp32 residual, both outputs, the w2 dual and norm_gamma work, K % 32 == 0.  precise, x_rep,
  * op_dtype = SM_OP_F16 and post_ln_* (up to 16 rows) are SM_EINVAL, and so is the fused RoPE + KV-append q|k|v product: an fp4 model runs the
  * plain q|k|v product and then the RoPE / append launch.  More than 16 rows expand the image to a packed bf16 scratch per call (shared with
- * the fp8 expansion) and run the bf16 kernels.  Measured against bf16 and fp8 weights at batch-1 decode: DESIGN.md, "MXFP4 weights". */
+ * the fp8 expansion) and run the bf16 kernels.  Measured against bf16 and fp8 weights at batch-1 decode: DESIGN.md, "MXFP4 weights".
+ *   w_dtype = SM_W_FP4_MFMA (same image) differs at 17..128 rows only: one launch requantises the rows (bf16 or fp32, K % 32 == 0, 16-byte aligned)
+ * into a per-HIP-stream workspace and a weight-streaming kernel reads the 4-bit codes once -- bias, act, fp32 residual, both outputs, the w2 dual and
+ * SM_ACT_SWIGLU_DUAL (N / 2 a multiple of 16, no bias) work; a call with precise or post_ln_* takes the expansion, the same weight-only product.
+ * SM_FP4_WSTREAM=0 in the environment forces the expansion (A/B). */
 size_t sm_packed_fp4_bytes(int N, int K);
 int sm_quant_pack_weight_fp4(const void* w_bf16, int N, int K, int ldw, void* out_packed_fp4, void* stream);
 int sm_unpack_weight_fp4(const void* packed_fp4, int N, int K, void* out_bf16, int ldo, void* stream);
@@ -363,7 +369,9 @@ int sm_model_set_fp8_mode(sm_model* m, int mode);
 /* MXFP4 weights (sm_quant_pack_weight_fp4) for the LLM's q|k|v, o, gate|up and down projections: 3.8 GB instead of 14.2 GB at Mistral-7B.  lm_head, the
  * embedding table, the gate, the connector and the tower keep their formats.  Valid between sm_model_create and the first sm_model_load_tensor; exclusive
  * with weights_fp8 and llm_fp16.  sm_llm_prefill / sm_llm_forward_logits expand the images per call above 16 rows, sm_llm_decode streams them as they are,
- * sm_group_llm_decode takes up to 16 active streams (one pass of the weight stream) and refuses more up front. */
+ * sm_group_llm_decode takes up to 16 active streams (one pass of the weight stream) and refuses more up front.
+ *   on = 1: as above.  on = 2: the same images with w_dtype = SM_W_FP4_MFMA -- chunks of 17..128 rows read the codes directly, and
+ * sm_group_llm_decode takes up to 128 active streams.  on = 0: off.  Any other value: SM_EINVAL. */
 int sm_model_set_weights_fp4(sm_model* m, int on);
 /* names of tensors still missing, '\n'-separated, into buf (for error messages) */
 int sm_model_missing(sm_model* m, char* buf, size_t buflen);

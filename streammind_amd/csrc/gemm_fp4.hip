@@ -1,6 +1,7 @@
 // MXFP4 (OCP MX v1.0: e2m1 elements, one e8m0 scale per 32 consecutive k of an output row) LLM weights: quantiser / packer,
-// unpacker, the bf16 expansion for calls with more than 16 rows, and the <= 16-row weight-streaming kernel on the CDNA4
-// block-scaled matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, A = e2m1 via cbsz 4, B = e4m3).
+// unpacker, the bf16 expansion for calls with more than 16 rows, the <= 16-row weight-streaming kernel on the CDNA4
+// block-scaled matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, A = e2m1 via cbsz 4, B = e4m3), and -- SM_W_FP4_MFMA --
+// the 17..128-row weight stream on the same instruction with the activations requantised once per call (at the end of the file).
 //
 // Image (common.h, "MXFP4 packed layout"): per 16-row group one contiguous stream of KS = ceil(K / 128) code chunks of 1 KiB
 // -- lane (g, i) of chunk ks holds the 32 codes of W[rg*16 + i][ks*128 + g*32 .. +31], i.e. ONE MX block, 16 bytes, which is
@@ -37,6 +38,11 @@
 // per CU at N = 4096.  More than a few rows are not tuned -- a 16-stream batched decode step takes 5.7 ms against 3.0 ms on fp8 (one-wave
 // blocks, every block requantising all rows): DESIGN.md, "MXFP4 weights".  The memory saving -- 3.8 GB instead of 14.2 GB of LLM
 // linears -- stands either way.
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <type_traits>
+
 #include "linear_common.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -437,4 +443,329 @@ int launch_skinny_fp4(const LinArgs& a, bool xf32, hipStream_t st) {
     else rc = launch_fp4_waves<1>(a, xf32, dual, qps, S, ws, ws2, st);
     if (rc || S == 1) return rc;
     return launch_splitk_reduce(a, ws, S, (a.N + 3) & ~3, st, ws2);
+}
+
+// ------------------------------------------------------------------------------------------------ 17..128 rows (SM_W_FP4_MFMA)
+// One pass over the 4-bit codes per call, the activations requantised ONCE per call and shared by every block (the <= 16-row kernel
+// requantises all rows in every block: 16 streams cost 5.7 ms per step there).
+//   Prepass (quant_rows_fp4x_kernel, grid (16-row fragments, K slices of four k-steps)): one thread per 32-block, quant32_hi_lo, written
+// fragment-major into a per-HIP-stream workspace [k-step][fragment][F4W_TILE]: a tile is 1 KiB of first halves of the e4m3 "hi" operand
+// (lane (g, i): row i, k = 16g .. 16g+15), 1 KiB of second halves (k = 64 + 16g ..), the same 2 KiB for "lo", then lane (G, i)'s two scale
+// bytes -- a B fragment is two 16-byte reads per lane and half, each 1 KiB contiguous per wave (no bank conflict, no shuffling).  The
+// fragment count is the main kernel's template value (2, 4, 8): rows >= M and k >= K are zero blocks with scale 127.
+//   Main kernel (wstream_fp4_kernel<MF, DUAL>, 384 threads, grid (column blocks, K slabs)) on the lines of wstream.hip:
+//   * W never touches LDS.  Each of the four consumer waves owns TWO 16-row weight groups (DUAL: the gate and the up group of the same 16
+//     columns, w and w2; else neighbours: a column block is 128 weight rows) and keeps a register ring of D = 2 quads per group in flight
+//     (17 KiB per wave, 68 KiB per block), non-temporal loads from HBM, the Quad of the <= 16-row kernel; the codes are the A operand as they are.
+//   * X goes through a two-stage LDS ring of k-steps (MF x 4224 B per stage: 33 KiB at 128 rows) filled by TWO loader waves from the
+//     workspace (L2 hits; a register ring of F4W_PF k-steps in flight), so the consumers' vmcnt queues hold HBM loads only.  One raw
+//     s_barrier per k-step hands stage t + 1 over and frees stage t - 1 (the loader writes exactly one k-step ahead: two stages suffice).
+//   * Each B fragment pair (hi, lo) read from LDS feeds four MFMAs (two weight groups x hi / lo): 64 B of ds_read per lane per four MFMAs.
+//     Accumulators: MF fragments x 4 floats per group; MF is a template value so 17..32 rows pay for two fragments, not eight.
+//   Arithmetic: at 128 rows a wave issues 32 block-scaled MFMAs per k-step against 2 KiB of codes (8 at 32 rows), which would bound the kernel
+// near 2.4 TB/s on the 4-bit bytes if a 16x16x128 e4m3 step took 64 clk.  Measured (tools/decode_bench.py --fp4-groups, one run on one box,
+// Mistral-7B shapes): gate | up streams at 2.2 / 1.4 / 0.85 TB/s at 32 / 64 / 128 rows, a batched decode step takes 3.78 / 5.27 / 8.44 ms against
+// 4.31 / 4.71 / 6.14 on bf16 -- ahead at 32 streams only.  Not the matrix pipe and not the x loads: without MFMAs, without MFMAs and B-fragment reads, and
+// without x loads (tools/experiments/wstream_fp4_probe.hip) gate | up at 128 rows goes 61.8 -> 56.2 / 46.3 / 56.7 us, without all three 33.9 -- the costs
+// add, i.e. the k-step is a serial chain between its two barriers with one consumer wave per SIMD ("MXFP4 weights").
+//   Grid: N = 4096 gives 32 column blocks, so the K quads are cut into up to 8 slabs (4 above 64 rows: a slab is M x N fp32 written and
+// read again) of at least two quads; slabs leave raw partial sums in the split-K workspace and launch_splitk_reduce applies the epilogue in
+// slab order (deterministic).  One slab: store4 in the kernel.  Ragged shapes follow the <= 16-row kernel: a short last quad re-reads the
+// last chunk and skips its MFMAs (every wave still meets the barrier), rows >= M / columns >= N are never stored.
+#define F4W_TILE 4224              // bytes per (k-step, 16-row fragment) of requantised x: 2 KiB hi + 2 KiB lo + 64 x (hi, lo) scale bytes
+#define F4W_PF 2                   // k-steps of x in flight per loader wave (registers)
+// experiment switches of tools/experiments/wstream_fp4_probe.hip (all 0 in the product): F4W_X_NOMFMA: no MFMAs (the operands are still consumed),
+// F4W_X_NOXREAD: no B-fragment reads from LDS, F4W_X_NOXLOAD: the loaders fetch nothing from the workspace (barriers and LDS writes stay)
+#ifndef F4W_X_NOMFMA
+#define F4W_X_NOMFMA 0
+#endif
+#ifndef F4W_X_NOXREAD
+#define F4W_X_NOXREAD 0
+#endif
+#ifndef F4W_X_NOXLOAD
+#define F4W_X_NOXLOAD 0
+#endif
+#define F4W_PREPASS_TAG (1LL << 62)  // sm_prof_read_tag key of the prepass launches: this | K
+
+template <bool XF32>
+__global__ __launch_bounds__(256) void quant_rows_fp4x_kernel(const void* __restrict__ x, int M, int K, int ldx, int MF, int KS, char* __restrict__ xq) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int mg = blockIdx.x, ks = blockIdx.y * 4 + wave;
+    if (ks >= KS) return;
+    const int i = lane >> 2, G = lane & 3, m = mg * 16 + i, k = ks * 128 + G * 32;     // a row's four blocks sit in neighbouring lanes: 256 / 512 B contiguous
+    float v[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) v[j] = 0.f;
+    if (m < M && k < K) {                                                // K % 32 == 0: whole blocks
+        const char* p = (const char*)x + ((size_t)m * ldx + k) * (XF32 ? 4 : 2);
+        if constexpr (XF32) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const f32x4 q = *(const f32x4*)(p + j * 16);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[4 * j + e] = q[e];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const u32x4 q = *(const u32x4*)(p + j * 16);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { v[8 * j + 2 * e] = bf2f(q[e] & 0xffff); v[8 * j + 2 * e + 1] = bf2f(q[e] >> 16); }
+            }
+        }
+    }
+    uint32_t hi[8], lo[8], sc;
+    quant32_hi_lo(v, hi, lo, sc);
+    // e4m3 operand map: block G's first 16 k are half G >> 1 of lane group 2 (G & 1), the next 16 the same half of the group after it
+    char* const tile = xq + ((size_t)ks * MF + mg) * F4W_TILE;
+    char* const d = tile + (G >> 1) * 1024 + ((G & 1) * 32 + i) * 16;
+    *(u32x4*)d = u32x4{hi[0], hi[1], hi[2], hi[3]};
+    *(u32x4*)(d + 256) = u32x4{hi[4], hi[5], hi[6], hi[7]};
+    *(u32x4*)(d + 2048) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    *(u32x4*)(d + 2048 + 256) = u32x4{lo[4], lo[5], lo[6], lo[7]};
+    *(uint16_t*)(tile + 4096 + (G * 16 + i) * 2) = (uint16_t)sc;
+}
+
+template <int MF, bool DUAL>
+__global__ __launch_bounds__(384) void wstream_fp4_kernel(LinArgs a, const char* __restrict__ xq, int qps, float* __restrict__ ws, float* __restrict__ ws2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];         // [2][MF][F4W_TILE]
+    constexpr int STG = MF * F4W_TILE, U = STG / 16, NL = (U + 127) / 128, D = 2;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int KS = (a.K + 127) >> 7, KQ = (KS + 3) >> 2;
+    const int q0 = blockIdx.y * qps, nq = min(KQ, q0 + qps) - q0;
+    const int ks0 = q0 * 4, nks = min(KS, ks0 + nq * 4) - ks0;         // k-steps that exist; every wave meets 1 + 4 nq barriers (whole quads)
+
+    if (wave >= 4) {
+        // ---- two loader waves: k-step t of the workspace (U 16-byte units, contiguous) into stage t & 1, unit l + 128 j per lane
+        const int l = (wave - 4) * 64 + lane;
+        const u32x4* const src = (const u32x4*)(xq + (size_t)ks0 * STG) + l;
+        u32x4 xr[F4W_PF][NL];
+        auto fetch = [&](int t, u32x4 (&r)[NL]) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j)
+                if ((j + 1) * 128 <= U || l + j * 128 < U) r[j] = F4W_X_NOXLOAD ? u32x4{0, 0, 0, 0} : src[(size_t)t * U + j * 128];
+        };
+        auto put = [&](int t, const u32x4 (&r)[NL]) {
+            u32x4* const dst = (u32x4*)(smem + (t & 1) * STG) + l;
+#pragma unroll
+            for (int j = 0; j < NL; ++j)
+                if ((j + 1) * 128 <= U || l + j * 128 < U) dst[j * 128] = r[j];
+        };
+        fetch(0, xr[0]);
+        if (1 < nks) fetch(1, xr[1]);
+        put(0, xr[0]);
+        if (2 < nks) fetch(2, xr[0]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                                   // stage 0 is in LDS
+        // iteration t (behind the barrier that published stage t): k-step t + 1 (ring slot (t + 1) % PF) into stage (t + 1) & 1 -- last read during
+        // k-step t - 1, closed by that barrier --, refill the slot with k-step t + 1 + PF, barrier (it publishes stage t + 1)
+        auto ltrip = [&](int t0, auto steady) {
+            constexpr bool STEADY = decltype(steady)::value;
+#pragma unroll
+            for (int d = 0; d < F4W_PF; ++d) {
+                const int t = t0 + d;
+                if (STEADY || t + 1 < nks) put(t + 1, xr[(d + 1) % F4W_PF]);
+                if (STEADY || t + 1 + F4W_PF < nks) fetch(t + 1 + F4W_PF, xr[(d + 1) % F4W_PF]);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        int t0 = 0;
+        for (; t0 + 2 * F4W_PF < nks; t0 += F4W_PF) ltrip(t0, std::true_type{});
+        for (; t0 < nq * 4; t0 += F4W_PF) ltrip(t0, std::false_type{});
+        return;
+    }
+
+    // ---- four consumer waves
+    const int i = lane & 15, g = lane >> 4;
+    const int rgA = DUAL ? blockIdx.x * 4 + wave : blockIdx.x * 8 + wave * 2, rgB = DUAL ? rgA : rgA + 1;
+    const size_t rgb = fp4_rg_bytes(KS);
+    const char* const wA = (const char*)a.w + (size_t)(rgA < a.NRG ? rgA : 0) * rgb;
+    const char* const wB = (const char*)(DUAL ? a.w2 : a.w) + (size_t)(rgB < a.NRG ? rgB : 0) * rgb;
+    struct Quad { u32x4 c[4]; uint32_t s; };
+    auto issue = [&](int c, Quad& qa, Quad& qb) {
+        const int q = q0 + c;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int ks = min(4 * q + h, KS - 1);                       // the last quad may be short: re-read, skipped below
+            qa.c[h] = __builtin_nontemporal_load((const u32x4*)(wA + (size_t)ks * 1024) + lane);
+            qb.c[h] = __builtin_nontemporal_load((const u32x4*)(wB + (size_t)ks * 1024) + lane);
+        }
+        qa.s = __builtin_nontemporal_load((const uint32_t*)(wA + (size_t)KS * 1024 + (size_t)q * 256) + lane);
+        qb.s = __builtin_nontemporal_load((const uint32_t*)(wB + (size_t)KS * 1024 + (size_t)q * 256) + lane);
+    };
+    f32x4 accA[MF], accB[MF];
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) accA[mf] = accB[mf] = f32x4{0, 0, 0, 0};
+    auto consume = [&](const Quad& qa, const Quad& qb, int c) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int t = 4 * c + h;
+            if (t < nks) {                                               // block-uniform
+                const char* const st = smem + (t & 1) * STG;
+                const i32x8 afA = {(int)qa.c[h][0], (int)qa.c[h][1], (int)qa.c[h][2], (int)qa.c[h][3], 0, 0, 0, 0};
+                const i32x8 afB = {(int)qb.c[h][0], (int)qb.c[h][1], (int)qb.c[h][2], (int)qb.c[h][3], 0, 0, 0, 0};
+                const int saA = (int)((qa.s >> (8 * h)) & 0xffu), saB = (int)((qb.s >> (8 * h)) & 0xffu);
+#pragma unroll
+                for (int mf = 0; mf < MF; ++mf) {
+                    const char* const xb = st + mf * F4W_TILE + lane * 16;
+                    u32x4 h0 = {0, 0, 0, 0}, h1 = h0, l0 = h0, l1 = h0;
+                    uint32_t sx = 0x7f7fu;
+                    if (!F4W_X_NOXREAD) {
+                        h0 = *(const u32x4*)xb; h1 = *(const u32x4*)(xb + 1024); l0 = *(const u32x4*)(xb + 2048); l1 = *(const u32x4*)(xb + 3072);
+                        sx = *(const uint16_t*)(st + mf * F4W_TILE + 4096 + lane * 2);
+                    }
+                    if (F4W_X_NOMFMA) {
+                        accA[mf] += __builtin_bit_cast(f32x4, (h0 ^ h1) + sx);
+                        accB[mf] += __builtin_bit_cast(f32x4, l0 ^ l1);
+                        if (mf == 0) { accA[0] += __builtin_bit_cast(f32x4, qa.c[h] + (uint32_t)saA); accB[0] += __builtin_bit_cast(f32x4, qb.c[h] + (uint32_t)saB); }
+                        continue;
+                    }
+                    const i32x8 bh = {(int)h0[0], (int)h0[1], (int)h0[2], (int)h0[3], (int)h1[0], (int)h1[1], (int)h1[2], (int)h1[3]};
+                    const i32x8 bl = {(int)l0[0], (int)l0[1], (int)l0[2], (int)l0[3], (int)l1[0], (int)l1[1], (int)l1[2], (int)l1[3]};
+                    const int sxh = (int)(sx & 0xffu), sxl = (int)(sx >> 8);
+                    // cbsz 4: A is e2m1 (its first four registers), blgp 0: B is e4m3; scale bytes in byte 0 of the scale operands
+                    accA[mf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(afA, bh, accA[mf], 4, 0, 0, saA, 0, sxh);
+                    accB[mf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(afB, bh, accB[mf], 4, 0, 0, saB, 0, sxh);
+                    accA[mf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(afA, bl, accA[mf], 4, 0, 0, saA, 0, sxl);
+                    accB[mf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(afB, bl, accB[mf], 4, 0, 0, saB, 0, sxl);
+                }
+            }
+            // this wave's reads of stage t have returned: the loaders may overwrite it behind the NEXT barrier; this one publishes stage t + 1
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+    };
+    Quad wq[D], wq2[D];
+    int done = 0, issued, live;
+    if (nq >= 2 * D) {                              // the ring proper, with a straight-line entry of its own (as skinny_fp4_kernel)
+#pragma unroll
+        for (int u = 0; u < D; ++u) issue(u, wq[u], wq2[u]);
+        __builtin_amdgcn_s_barrier();               // stage 0 is in LDS
+        asm volatile("" ::: "memory");
+        issued = live = D;
+        for (; issued + D <= nq; issued += D, done += D) {
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                consume(wq[u], wq2[u], done + u);
+                issue(issued + u, wq[u], wq2[u]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    } else {
+        issued = live = min(nq, D);
+#pragma unroll
+        for (int u = 0; u < D; ++u)
+            if (u < live) issue(u, wq[u], wq2[u]);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    }
+    const int rem = nq - issued;                    // < D quads left: each takes the registers of the quad just consumed
+#pragma unroll
+    for (int u = 0; u < D; ++u)
+        if (u < live) {
+            consume(wq[u], wq2[u], done + u);
+            if (u < rem) issue(issued + u, wq[u], wq2[u]);
+        }
+#pragma unroll
+    for (int u = 0; u < D - 1; ++u)
+        if (u < rem) consume(wq[u], wq2[u], issued + u);
+
+    // ---- epilogue.  acc[mf]: lane (g, i) holds n = rg * 16 + 4g + 0..3 of row m = mf * 16 + i; rows >= M / columns >= N are not stored
+    const int nA = rgA * 16 + g * 4, nB = rgB * 16 + g * 4, ldw = (a.N + 3) & ~3;
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) {
+        const int m = mf * 16 + i;
+        if (m >= a.M) continue;
+        if (ws) {                                   // K slabs: raw partial sums into slab blockIdx.y, [m][N padded to 4]
+            const size_t o = ((size_t)blockIdx.y * a.M + m) * ldw;
+            for (int r = 0; r < 4; ++r) {
+                if (nA + r < a.N) ws[o + nA + r] = accA[mf][r];
+                if (nB + r < a.N) (DUAL ? ws2 : ws)[o + nB + r] = accB[mf][r];
+            }
+        } else if (DUAL) {
+            const f32x4 up = accB[mf];              // (a copy: &accB[mf] made the whole array address-taken and put it into scratch, MFMA loop included)
+            store4(a, m, nA, accA[mf], &up);
+        } else {
+            store4(a, m, nA, accA[mf], nullptr);
+            store4(a, m, nB, accB[mf], nullptr);
+        }
+    }
+}
+
+// per-HIP-stream workspace of the requantised activations (grown on demand; steady state allocates nothing)
+static std::mutex g_x4_mu;
+static std::map<hipStream_t, std::pair<void*, size_t>> g_x4;
+void release_fp4_workspace(hipStream_t st) {
+    std::lock_guard<std::mutex> lk(g_x4_mu);
+    auto e = g_x4.find(st);
+    if (e != g_x4.end()) { if (e->second.first) (void)hipFree(e->second.first); g_x4.erase(e); }
+}
+
+template <int MF>
+static int launch_wstream_fp4_mf(const LinArgs& a, bool xf32, hipStream_t st) {
+    const bool dual = a.w2 != nullptr;
+    const int KS = (a.K + 127) / 128, KQ = (KS + 3) / 4;
+    const size_t need = (size_t)KS * MF * F4W_TILE;
+    char* xq;
+    {
+        std::lock_guard<std::mutex> lk(g_x4_mu);
+        auto& e = g_x4[st];
+        if (e.second < need) {
+            if (e.first) { SM_HIP(hipStreamSynchronize(st)); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
+            SM_HIP(hipMalloc(&e.first, need));
+            e.second = need;
+        }
+        xq = (char*)e.first;
+    }
+    {   // (profiling tags: the prepass under F4W_PREPASS_TAG | K, the product with its slab sum under the shape tag of the other weight streams)
+        SmProfScope prof(SM_PROF_SKINNY, st, F4W_PREPASS_TAG | (unsigned)a.K);
+        const dim3 qgrid(MF, (KS + 3) / 4);
+        if (xf32) quant_rows_fp4x_kernel<true><<<qgrid, 256, 0, st>>>(a.x, a.M, a.K, a.ldx, MF, KS, xq);
+        else quant_rows_fp4x_kernel<false><<<qgrid, 256, 0, st>>>(a.x, a.M, a.K, a.ldx, MF, KS, xq);
+        SM_LAUNCH_CHECK();
+    }
+    SmProfScope prof(SM_PROF_SKINNY, st, ((long long)a.N << 32) | (unsigned)a.K);
+    // K slabs: fill 256 CUs, at least two quads per slab, at most 8 slabs (4 above 64 rows: every slab is M x N fp32 written and read again)
+    const int CB = dual ? cdiv(a.NRG, 4) : cdiv(a.NRG, 8);
+    int S = std::min(std::min(MF > 4 ? 4 : 8, cdiv(256, CB)), std::max(1, KQ / 2));
+    const int qps = cdiv(KQ, S);
+    S = cdiv(KQ, qps);
+    float *ws = nullptr, *ws2 = nullptr;
+    if (S > 1) {
+        const size_t slab = (size_t)S * a.M * ((a.N + 3) & ~3);
+        int rc = splitk_workspace(st, slab * sizeof(float) * (dual ? 2 : 1), &ws);
+        if (rc) return rc;
+        if (dual) ws2 = ws + slab;
+    }
+    constexpr size_t sh = 2 * (size_t)MF * F4W_TILE;
+    if (sh > 64 * 1024) {                           // (MF = 8: 66 KiB, above the default limit; a function attribute is per device: set once on each)
+        static std::mutex mu;
+        static bool attr_set[64] = {};
+        int dev = 0;
+        SM_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+            SM_HIP(hipFuncSetAttribute((const void*)wstream_fp4_kernel<MF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            SM_HIP(hipFuncSetAttribute((const void*)wstream_fp4_kernel<MF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            if (dev >= 0 && dev < 64) attr_set[dev] = true;
+        }
+    }
+    const dim3 grid(CB, S);
+    if (dual) wstream_fp4_kernel<MF, true><<<grid, 384, sh, st>>>(a, xq, qps, ws, ws2);
+    else wstream_fp4_kernel<MF, false><<<grid, 384, sh, st>>>(a, xq, qps, ws, ws2);
+    SM_LAUNCH_CHECK();
+    if (S == 1) return SM_OK;
+    return launch_splitk_reduce(a, ws, S, (a.N + 3) & ~3, st, ws2);
+}
+
+// sm_linear with SM_W_FP4_MFMA and 17..128 rows (linear.hip validated the call)
+int launch_wstream_fp4(const LinArgs& a, bool xf32, hipStream_t st) {
+    if (a.M <= 32) return launch_wstream_fp4_mf<2>(a, xf32, st);
+    if (a.M <= 64) return launch_wstream_fp4_mf<4>(a, xf32, st);
+    return launch_wstream_fp4_mf<8>(a, xf32, st);
 }

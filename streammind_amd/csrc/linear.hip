@@ -1215,6 +1215,7 @@ void release_stream_workspaces(hipStream_t st) {
         }
     }
     release_fp8_workspace(st);
+    release_fp4_workspace(st);
 }
 static int dequant_workspace(hipStream_t st, int which, size_t bytes, void** out) {
     std::lock_guard<std::mutex> lk(g_ws_mu);
@@ -1670,6 +1671,17 @@ static int rowsplit_rows(const sm_linear_t* p) {
     return rows_main * 256;
 }
 
+// SM_W_FP4_MFMA at 17..128 rows: the prepass + weight stream of gemm_fp4.hip, unless the call sets a field that kernel does not carry -- then the
+// expansion below runs, the same weight-only product.  SM_FP4_WSTREAM=0: always the expansion (A/B)
+static bool fp4_wstream_takes(const sm_linear_t* p) {
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("SM_FP4_WSTREAM"); on = e ? atoi(e) : 1; }
+    const bool xf32 = p->x_dtype == SM_X_F32;
+    return on && p->w_dtype == SM_W_FP4_MFMA && p->M > 16 && p->M <= 128 && p->op_dtype == SM_OP_BF16 && !p->vt && p->remap_in == 0 && p->x_rep <= 1 && !p->precise &&
+           !p->norm_gamma && !p->post_ln_gamma && !p->fold_stats_in && !p->fold_stats_out && !p->tile_hint && (p->K & 31) == 0 && p->ldx >= p->K &&
+           (p->ldx % (xf32 ? 4 : 8)) == 0 && ((uintptr_t)p->x & 15) == 0;
+}
+
 extern "C" int sm_linear(const sm_linear_t* p, void* stream) {
     SM_REQUIRE(p, "sm_linear: null args");
     if (const int m1 = rowsplit_rows(p)) {
@@ -1686,6 +1698,15 @@ extern "C" int sm_linear(const sm_linear_t* p, void* stream) {
         SM_REQUIRE(p->M > 16 && p->x_dtype == SM_X_BF16 && p->out_bf16 && !p->out_f32 && !p->residual && !p->vt && !p->w2 && p->remap_in == 0 && !p->post_ln_gamma &&
                    !p->norm_gamma && (p->N & 1) == 0 && p->ldo_bf16 >= F,
                    "sm_linear: SM_ACT_SWIGLU_DUAL needs M > 16, 16-bit x, one [gate | up] weight image (N even) and a 16-bit output [M][ldo_bf16 >= N / 2] only");
+        if (fp4_wstream_takes(p) && !p->bias && (F & 15) == 0) {
+            // the fp4 weight stream pairs the gate and the up group of a column in one wave: the [gate | up] image as w and w2 (a fused image is the
+            // concatenation of its parts' row groups)
+            sm_linear_t q = *p;
+            q.act = SM_ACT_NONE; q.N = F;
+            q.w2 = (const char*)p->w + (size_t)(F / 16) * fp4_rg_bytes((p->K + 127) / 128);
+            bool dummy = false;
+            return linear_impl(&q, stream, &dummy);
+        }
         static int dual_fuse = -1;                    // SM_SWIGLU_FUSE=0: always the product + the SwiGLU pass (A/B)
         if (dual_fuse < 0) { const char* e = getenv("SM_SWIGLU_FUSE"); dual_fuse = e ? atoi(e) : 1; }
         const int bn = gemm_tile_choice(p);
@@ -1757,12 +1778,13 @@ static int linear_impl(const sm_linear_t* p, void* stream, bool* ln_done) {
     const bool w8_any = p->w_dtype == SM_W_FP8 || p->w_dtype == SM_W_FP8_MFMA;
     const bool lds64 = (sm_skinny_lds64_on() >= 2 || (sm_skinny_lds64_on() == 1 && w8_any)) && p->M > 32 && p->M <= 64 && p->x_dtype == SM_X_BF16 && !p->precise && !p->norm_gamma && ((p->N & 3) == 0 || p->N < 4) && a.KS >= 8 &&
                        p->remap_in == 0 && !p->vt && (p->ldx % 8) == 0 && p->act != SM_ACT_SWIGLU_DUAL;
-    SM_REQUIRE(!p->w2 || p->M <= 32 || lds64, "sm_linear: dual weights only on the weight-streaming path (M <= 32; 16-bit rows up to 64)");
+    const bool f4w = fp4_wstream_takes(p) && p->act != SM_ACT_SWIGLU_DUAL;
+    SM_REQUIRE(!p->w2 || p->M <= 32 || lds64 || f4w, "sm_linear: dual weights only on the weight-streaming path (M <= 32; 16-bit rows up to 64)");
     SM_REQUIRE(p->x_rep > 1 || p->ldx >= a.KS * 32, "sm_linear: ldx=%d must cover K padded to 32 (%d)", p->ldx, a.KS * 32);
     SM_REQUIRE(!p->vt || (p->vt_dh > 0 && p->vt_S > 0 && (p->N - p->vt_n0) % p->vt_dh == 0), "sm_linear: bad vt args");
     hipStream_t st = (hipStream_t)stream;
     const bool xf32 = p->x_dtype == SM_X_F32;
-    if (p->w_dtype == SM_W_FP4) {
+    if (p->w_dtype == SM_W_FP4 || p->w_dtype == SM_W_FP4_MFMA) {
         // MXFP4 weights (gemm_fp4.hip).  Up to 16 rows: the block-scaled MFMA weight stream; what that kernel does not do is refused, never
         // replaced by a different product.  More rows: the image is expanded to a packed bf16 scratch and the bf16 kernels below run on it.
         SM_REQUIRE(p->op_dtype == SM_OP_BF16, "sm_linear: fp4 weights take bf16 operands (op_dtype SM_OP_F16 is not supported)");
@@ -1775,6 +1797,7 @@ static int linear_impl(const sm_linear_t* p, void* stream, bool* ln_done) {
             SmProfScope prof(SM_PROF_SKINNY, st, ((long long)p->N << 32) | (unsigned)p->K);
             return launch_skinny_fp4(a, xf32, st);
         }
+        if (f4w) return launch_wstream_fp4(a, xf32, st);      // SM_W_FP4_MFMA, 17..128 rows: x requantised once, one pass over the codes
         const void *d0 = nullptr, *d1 = nullptr;
         int rc = dequant_fp4(st, 0, p->w, p->N, p->K, &d0);
         if (!rc && p->w2) rc = dequant_fp4(st, 1, p->w2, p->N, p->K, &d1);

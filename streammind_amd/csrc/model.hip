@@ -133,7 +133,7 @@ struct Slot {            // one tensor the path reads
 
 struct sm_model {
     sm_config_t c;
-    bool weights_fp4 = false;      // sm_model_set_weights_fp4 (not part of sm_config_t: the struct is ABI)
+    int weights_fp4 = 0;           // sm_model_set_weights_fp4's mode: 0 off, 1 SM_W_FP4, 2 SM_W_FP4_MFMA (not part of sm_config_t: the struct is ABI)
     bool any_loaded = false;       // a tensor has been handed over: the weight formats are fixed from here on
     std::unordered_map<std::string, Slot> slots;           // canonical name -> storage
     struct Route { std::string slot; int row0; int rows; int part; };   // checkpoint name -> (slot, first row, row count, index of this part)
@@ -606,16 +606,18 @@ extern "C" int sm_model_set_weights_fp4(sm_model* m, int on) {
     SM_REQUIRE(m && !m->any_loaded && !m->finalized, "sm_model_set_weights_fp4: call it between sm_model_create and the first sm_model_load_tensor");
     SM_REQUIRE(!on || (!m->c.weights_fp8 && !m->c.llm_fp16), "sm_model_set_weights_fp4: exclusive with weights_fp8 and llm_fp16");
     SM_REQUIRE(!on || m->c.llm_layers == 0 || ((m->c.llm_hidden & 31) == 0 && (m->c.llm_mlp & 31) == 0), "sm_model_set_weights_fp4: llm_hidden and llm_mlp must be multiples of 32");
-    m->weights_fp4 = on != 0;
+    SM_REQUIRE(on >= 0 && on <= 2, "sm_model_set_weights_fp4: mode %d (0 off, 1 expansion above 16 rows, 2 the fp4 weight stream up to 128 rows)", on);
+    m->weights_fp4 = on;
     for (auto& kv : m->slots)
-        if (kv.second.kind == 1 && kv.first.rfind("llm.model.layers.", 0) == 0) kv.second.fp4 = m->weights_fp4;
+        if (kv.second.kind == 1 && kv.first.rfind("llm.model.layers.", 0) == 0) kv.second.fp4 = on != 0;
     return SM_OK;
 }
 extern "C" int sm_norm_ex(const float* x, int M, int D, int ldx, const float* gamma, const float* beta, float eps, int post_act,
                           float* out_f32, void* out_bf16, int ldo, int op_dtype, void* stream);
-// sm_linear; where the product's kernel does not carry the norm of the finished rows (fp4 weights up to 16 rows) the norm is the launch behind it
+// sm_linear; where the product's kernel does not carry the norm of the finished rows (fp4 weights up to 16 rows, SM_W_FP4_MFMA up to 128) the norm is the launch behind it
 static int linear_post_norm(const sm_linear_t& a, void* stream) {
-    if (a.w_dtype != SM_W_FP4 || a.M > 16 || !a.post_ln_gamma) return sm_linear(&a, stream);
+    const bool peel = (a.w_dtype == SM_W_FP4 && a.M <= 16) || (a.w_dtype == SM_W_FP4_MFMA && a.M <= 128);
+    if (!peel || !a.post_ln_gamma) return sm_linear(&a, stream);
     sm_linear_t b = a;
     b.post_ln_gamma = nullptr; b.post_ln_out = nullptr; b.post_ln_out_f32 = nullptr;
     const int rc = sm_linear(&b, stream);
@@ -628,7 +630,7 @@ static sm_linear_t lin(const sm_model* m, const Slot& w, const void* x, int x_dt
     sm_linear_t a;
     memset(&a, 0, sizeof(a));
     a.w = w.buf.p; a.N = w.N; a.K = w.K; a.x = x; a.x_dtype = x_dtype; a.M = M; a.ldx = ldx;
-    if (w.fp4) a.w_dtype = SM_W_FP4;
+    if (w.fp4) a.w_dtype = m->weights_fp4 == 2 ? SM_W_FP4_MFMA : SM_W_FP4;
     if (w.fp8) { a.w_dtype = m->c.weights_fp8 == 2 && !w.wo ? SM_W_FP8_MFMA : SM_W_FP8; a.w_scale = w.scale.as<float>(); }
     if (w.f16) a.op_dtype = SM_OP_F16;
     return a;
@@ -1590,8 +1592,8 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
     // linears on the tiled MFMA GEMM (M = streams) -- still ONE pass over the weights per step -- and the per-stream kernels (token gather,
     // RoPE + KV append, attention, arg-max: per-stream pointers travel by value, SM_MAX_SEG at a time) in chunks
     // (fp8 weights: the weight-streaming kernels read the fp8 image up to 64 rows; beyond that a product would expand it to bf16 per call)
-    // (fp4 weights: one pass of the block-scaled weight stream, up to 16 rows)
-    const int s_cap = m->weights_fp4 ? 16 : c.weights_fp8 == 2 ? 16 : c.weights_fp8 ? (sm_skinny_lds64_on() ? 64 : SM_MAX_SEG) : SM_GROUP_DECODE_MAX;
+    // (fp4 weights: one pass of the block-scaled weight stream, up to 16 rows; mode 2: up to 128 with the activations requantised once per product)
+    const int s_cap = m->weights_fp4 == 2 ? 128 : m->weights_fp4 ? 16 : c.weights_fp8 == 2 ? 16 : c.weights_fp8 ? (sm_skinny_lds64_on() ? 64 : SM_MAX_SEG) : SM_GROUP_DECODE_MAX;
     SM_REQUIRE(S <= s_cap, "sm_group_llm_decode: %d active streams exceed one weight pass (%d)", S, s_cap);
     const int ld = c.llm_hidden, H = c.llm_heads, KV = c.llm_kv_heads, dh = ld / H, qn = H * dh, kn = KV * dh, V = c.llm_vocab;
     // the per-stream kernels of a step take ONE cache pitch (V^T row stride) for all their streams: the active streams are brought to a common capacity --

@@ -127,7 +127,7 @@ def load_pretrained_model(model_path, model_base=None, model_name="VideoLLaMA2-7
     if tdt not in (torch.float16, torch.bfloat16):
         raise ValueError(f"torch_dtype must be torch.float16 or torch.bfloat16, got {tdt}")
     w8 = bool(kwargs.pop("weights_fp8", False))
-    w4 = bool(kwargs.pop("weights_fp4", False))             # the LLM's linears as MXFP4 images: bf16 operands for the LLM, as with fp8
+    w4 = int(kwargs.pop("weights_fp4", 0))                  # the LLM's linears as MXFP4 images: bf16 operands for the LLM, as with fp8
     if w8 and w4:
         raise ValueError("weights_fp8 and weights_fp4 are exclusive")
     over = dict(max_frames_per_call=kwargs.pop("max_frames_per_call", 8), weights_fp8=w8, weights_fp4=w4, llm_fp16=(tdt == torch.float16 and not w8 and not w4), proj_fp16=(tdt == torch.float16 and not w8),

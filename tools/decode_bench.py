@@ -1,7 +1,10 @@
 """Mistral-7B decode-only micro-benchmark (for rocprofv3 kernel traces of the decode step).
 --fp4 [n_new]: batch-1 decode on bf16, fp8 and MXFP4 weights in ONE run on one box, the formats alternating over three rounds: tokens/s (median), the
 fraction of the HBM roof on each format's own bytes per token, the summed HIP-event time of the weight-streaming launches per token, the same per
-product shape (us per launch, TB/s on the product's own weight bytes), and ms per batched decode step at 4 / 8 / 16 streams."""
+product shape (us per launch, TB/s on the product's own weight bytes), and ms per batched decode step at 4 / 8 / 16 streams; then the wide groups.
+--fp4-groups: only the wide groups -- batched decode at 32 / 64 / 128 streams on bf16, fp8 (32, 64: its cap) and MXFP4 mode 2 (weights_fp4=2: the fp4
+weight stream of 17..128 rows), the formats alternating over three rounds (median ms per step), and for fp4 the HIP-event time of every product of a
+layer (us per launch incl. its slab sum, TB/s on the product's own 4.25-bit bytes) and of the activation prepass launches (their share of a step)."""
 import ctypes as C
 import json, os, statistics, sys, time
 import torch
@@ -10,14 +13,57 @@ import bench
 from streammind_amd.native import NativeModel, PathConfig
 
 
+def make_model(**kw):
+    cfg = PathConfig(llm_layers=32, max_frames_per_call=1, vit_layers=2, **kw)
+    m = NativeModel(cfg)
+    bench.random_weights_into(m, cfg, 1)
+    bench.random_llm_weights_into(m, cfg, 2)
+    m.finalize()
+    return cfg, m
+
+
+def wide_groups(rounds=3):
+    legs = {name: make_model(**kw) for name, kw in (("bf16", {}), ("fp8", dict(weights_fp8=1)), ("fp4", dict(weights_fp4=2)))}
+    sizes = {"bf16": (32, 64, 128), "fp8": (32, 64), "fp4": (32, 64, 128)}
+    ms = {name: {S: [] for S in sizes[name]} for name in legs}
+    for _ in range(rounds):                                                     # alternate: a drifting box hits every format alike
+        for name, (cfg, m) in legs.items():
+            grp = bench.group_decode_leg(m, cfg, sizes=sizes[name], n_new=32)
+            for S, t in zip(grp["streams"], grp["ms_per_step"]):
+                ms[name][S].append(t)
+    out = {name: {S: {"ms_per_step": statistics.median(v), "runs": v} for S, v in per.items()} for name, per in ms.items()}
+    cfg, m = legs["fp4"]                                                        # fp4: HIP events around every weight-streaming launch of 8 steps
+    g = torch.Generator(device="cuda").manual_seed(17)
+    streams = []
+    for S in sizes["fp4"]:
+        while len(streams) < S:
+            st = m.open_stream(max_frames=8, max_seq=1024)
+            st.prefill(torch.randint(3, cfg.llm_vocab, (328,), generator=g, device="cuda", dtype=torch.int32))
+            streams.append(st)
+        grp = m.open_group(streams)
+        grp.decode(4); torch.cuda.synchronize()
+        m.lib.sm_prof_reset(); m.lib.sm_prof_enable(1 << 1)
+        grp.decode(8); torch.cuda.synchronize()
+        m.lib.sm_prof_enable(0)
+        grp.close()
+        per, bpw = {}, 0.5 + 1 / 32
+        for label, tag, byts in (("qkv", (6144 << 32) | 4096, 6144 * 4096 * bpw), ("o", (4096 << 32) | 4096, 4096 * 4096 * bpw), ("gate_up", (14336 << 32) | 4096, 2 * 14336 * 4096 * bpw),
+                                 ("down", (4096 << 32) | 14336, 4096 * 14336 * bpw), ("prepass_k4096", (1 << 62) | 4096, 0), ("prepass_k14336", (1 << 62) | 14336, 0)):
+            c2, m2 = C.c_int(), C.c_float()
+            m.lib.sm_prof_read_tag(1, C.c_longlong(tag), C.byref(c2), C.byref(m2))
+            if c2.value:
+                us = m2.value * 1e3 / c2.value
+                per[label] = {"launches_per_step": c2.value // 8, "us": round(us, 2), "ms_per_step": round(m2.value / 8, 4)}
+                if byts:
+                    per[label]["tb_s"] = round(byts / us / 1e6, 2)
+        out["fp4"][S]["per_product"] = per
+    print(json.dumps({"group_decode_wide": out}))
+
+
 def three_formats(n_new):
     d, legs = 4096, {}
     for name, kw in (("bf16", {}), ("fp8", dict(weights_fp8=1)), ("fp4", dict(weights_fp4=True))):
-        cfg = PathConfig(llm_layers=32, max_frames_per_call=1, vit_layers=2, **kw)
-        m = NativeModel(cfg)
-        bench.random_weights_into(m, cfg, 1)
-        bench.random_llm_weights_into(m, cfg, 2)
-        m.finalize()
+        cfg, m = make_model(**kw)
         legs[name] = (cfg, m, m.open_stream(max_frames=1024, max_seq=1024))
     lin = 32 * (d * d * 2 + 2 * d * 1024 + 3 * d * 14336)                      # weights of the LLM's linears
     wbytes = {"bf16": 2.0 * lin, "fp8": 1.0 * lin + 4 * 32 * (6144 + 4096 + 28672 + 4096), "fp4": lin * (0.5 + 1 / 32)}
@@ -50,8 +96,15 @@ def three_formats(n_new):
         out[name] = {"per_shape": shapes, "tokens_per_s": round(t, 1), "runs": tps[name], "bytes_per_token": byts, "hbm_frac": round(byts * t / 1e9 / bench.HBM_PEAK_GBS, 4),
                      "weight_stream_ms_per_token": round(ms.value / 32, 4), "weight_stream_launches_per_token": cnt.value // 32, "ms_per_token": round(1e3 / t, 4)}
     print(json.dumps({"decode_three_formats": out}))
+    del legs, out, m, s, cfg, grp                                               # (the streams hold their models: drop every name before the next three are built)
+    import gc
+    gc.collect(); torch.cuda.empty_cache()
+    wide_groups()
 
 
+if "--fp4-groups" in sys.argv:
+    wide_groups()
+    sys.exit(0)
 if "--fp4" in sys.argv:
     i = sys.argv.index("--fp4")
     three_formats(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 128)
