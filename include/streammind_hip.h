@@ -44,6 +44,8 @@ extern "C" {
 #define SM_W_FP4 3        /* the sm_quant_pack_weight_fp4 image (OCP MXFP4: e2m1 codes + one e8m0 scale per 32 k, scales inside the image) */
 #define SM_W_FP4_MFMA 4   /* the SM_W_FP4 image; calls with 17..128 rows quantise the activations once (e4m3 hi + lo per 32-block) and stream the codes
                            * through the block-scaled MFMA (gemm_fp4.hip, "17..128 rows"); <= 16 rows and > 128 rows are SM_W_FP4 */
+#define SM_W_FP4_GEMM 5   /* the SM_W_FP4 image; up to 128 rows SM_W_FP4_MFMA exactly, at 129..512 rows the same activation prepass and a tiled block-scaled
+                           * MFMA GEMM on the codes (gemm_fp4.hip, "above 128 rows"): no bf16 expansion of the image; more rows: the expansion (measured bound) */
 #define SM_OP_BF16 0  /* 16-bit operands (packed weights, x, 16-bit outputs) are bfloat16 */
 #define SM_OP_F16 1   /* ... IEEE half: tiled GEMM only (the ViT's optional fp16 mode = the reference demo's precision, builder.py:54) */
 #define SM_TILE_AUTO 0
@@ -84,7 +86,11 @@ int sm_quant_pack_weight_fp8(const void* w_bf16, int N, int K, int ldw, void* ou
  *   w_dtype = SM_W_FP4_MFMA (same image) differs at 17..128 rows only: one launch requantises the rows (bf16 or fp32, K % 32 == 0, 16-byte aligned)
  * into a per-HIP-stream workspace and a weight-streaming kernel reads the 4-bit codes once -- bias, act, fp32 residual, both outputs, the w2 dual and
  * SM_ACT_SWIGLU_DUAL (N / 2 a multiple of 16, no bias) work; a call with precise or post_ln_* takes the expansion, the same weight-only product.
- * SM_FP4_WSTREAM=0 in the environment forces the expansion (A/B). */
+ * SM_FP4_WSTREAM=0 in the environment forces the expansion (A/B).
+ *   w_dtype = SM_W_FP4_GEMM (same image) is SM_W_FP4_MFMA up to 128 rows (same kernels, same bits); at 129..512 rows (above that the expansion is faster: DESIGN.md) the same prepass feeds a tiled
+ * GEMM that reads the 4-bit codes through LDS: the error class of the 17..128-row path, fp32 rows included, and no expansion.  It carries what the weight
+ * stream carries (bias, act, fp32 residual, both outputs, the w2 dual, SM_ACT_SWIGLU_DUAL with N / 2 a multiple of 16 and no bias); any other call takes
+ * the expansion as SM_W_FP4_MFMA does.  SM_FP4_GEMM=0 in the environment forces the expansion (A/B). */
 size_t sm_packed_fp4_bytes(int N, int K);
 int sm_quant_pack_weight_fp4(const void* w_bf16, int N, int K, int ldw, void* out_packed_fp4, void* stream);
 int sm_unpack_weight_fp4(const void* packed_fp4, int N, int K, void* out_bf16, int ldo, void* stream);
@@ -373,6 +379,10 @@ int sm_model_set_fp8_mode(sm_model* m, int mode);
  *   on = 1: as above.  on = 2: the same images with w_dtype = SM_W_FP4_MFMA -- chunks of 17..128 rows read the codes directly, and
  * sm_group_llm_decode takes up to 128 active streams.  on = 0: off.  Any other value: SM_EINVAL. */
 int sm_model_set_weights_fp4(sm_model* m, int on);
+/* weights_fp4 = 2 models: on = 1 hands the LLM's fp4 linears to sm_linear as SM_W_FP4_GEMM -- prefill chunks and teacher-forced evaluation
+ * of 129..512 rows run the tiled fp4 GEMM instead of expanding every image per call; everything up to 128 rows is unchanged.  Valid in the window of
+ * sm_model_set_weights_fp4, after it; on = 0: off (the default).  SM_EINVAL unless on is 0 or 1, and for on = 1 without weights_fp4 = 2. */
+int sm_model_set_fp4_gemm(sm_model* m, int on);
 /* names of tensors still missing, '\n'-separated, into buf (for error messages) */
 int sm_model_missing(sm_model* m, char* buf, size_t buflen);
 

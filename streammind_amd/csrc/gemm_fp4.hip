@@ -1,7 +1,8 @@
 // MXFP4 (OCP MX v1.0: e2m1 elements, one e8m0 scale per 32 consecutive k of an output row) LLM weights: quantiser / packer,
 // unpacker, the bf16 expansion for calls with more than 16 rows, the <= 16-row weight-streaming kernel on the CDNA4
-// block-scaled matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, A = e2m1 via cbsz 4, B = e4m3), and -- SM_W_FP4_MFMA --
-// the 17..128-row weight stream on the same instruction with the activations requantised once per call (at the end of the file).
+// block-scaled matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, A = e2m1 via cbsz 4, B = e4m3), -- SM_W_FP4_MFMA -- the
+// 17..128-row weight stream on the same instruction with the activations requantised once per call, and -- SM_W_FP4_GEMM -- the
+// tiled GEMM for more than 128 rows on the same prepass (both at the end of the file).
 //
 // Image (common.h, "MXFP4 packed layout"): per 16-row group one contiguous stream of KS = ceil(K / 128) code chunks of 1 KiB
 // -- lane (g, i) of chunk ks holds the 32 codes of W[rg*16 + i][ks*128 + g*32 .. +31], i.e. ONE MX block, 16 bytes, which is
@@ -706,10 +707,9 @@ void release_fp4_workspace(hipStream_t st) {
     if (e != g_x4.end()) { if (e->second.first) (void)hipFree(e->second.first); g_x4.erase(e); }
 }
 
-template <int MF>
-static int launch_wstream_fp4_mf(const LinArgs& a, bool xf32, hipStream_t st) {
-    const bool dual = a.w2 != nullptr;
-    const int KS = (a.K + 127) / 128, KQ = (KS + 3) / 4;
+// the prepass: the rows of a call requantised into the stream's workspace as MF fragments per k-step (rows >= M: zero blocks)
+static int requant_rows_fp4(const LinArgs& a, bool xf32, int MF, int prof_cls, hipStream_t st, char** out) {
+    const int KS = (a.K + 127) / 128;
     const size_t need = (size_t)KS * MF * F4W_TILE;
     char* xq;
     {
@@ -723,12 +723,22 @@ static int launch_wstream_fp4_mf(const LinArgs& a, bool xf32, hipStream_t st) {
         xq = (char*)e.first;
     }
     {   // (profiling tags: the prepass under F4W_PREPASS_TAG | K, the product with its slab sum under the shape tag of the other weight streams)
-        SmProfScope prof(SM_PROF_SKINNY, st, F4W_PREPASS_TAG | (unsigned)a.K);
+        SmProfScope prof(prof_cls, st, F4W_PREPASS_TAG | (unsigned)a.K);
         const dim3 qgrid(MF, (KS + 3) / 4);
         if (xf32) quant_rows_fp4x_kernel<true><<<qgrid, 256, 0, st>>>(a.x, a.M, a.K, a.ldx, MF, KS, xq);
         else quant_rows_fp4x_kernel<false><<<qgrid, 256, 0, st>>>(a.x, a.M, a.K, a.ldx, MF, KS, xq);
         SM_LAUNCH_CHECK();
     }
+    *out = xq;
+    return SM_OK;
+}
+
+template <int MF>
+static int launch_wstream_fp4_mf(const LinArgs& a, bool xf32, hipStream_t st) {
+    const bool dual = a.w2 != nullptr;
+    const int KS = (a.K + 127) / 128, KQ = (KS + 3) / 4;
+    char* xq;
+    if (int rc = requant_rows_fp4(a, xf32, MF, SM_PROF_SKINNY, st, &xq)) return rc;
     SmProfScope prof(SM_PROF_SKINNY, st, ((long long)a.N << 32) | (unsigned)a.K);
     // K slabs: fill 256 CUs, at least two quads per slab, at most 8 slabs (4 above 64 rows: every slab is M x N fp32 written and read again)
     const int CB = dual ? cdiv(a.NRG, 4) : cdiv(a.NRG, 8);
@@ -768,4 +778,200 @@ int launch_wstream_fp4(const LinArgs& a, bool xf32, hipStream_t st) {
     if (a.M <= 32) return launch_wstream_fp4_mf<2>(a, xf32, st);
     if (a.M <= 64) return launch_wstream_fp4_mf<4>(a, xf32, st);
     return launch_wstream_fp4_mf<8>(a, xf32, st);
+}
+
+// ------------------------------------------------------------------------------------------------ above 128 rows (SM_W_FP4_GEMM)
+// A tiled GEMM on the lines of gemm_fp8_kernel: above 128 rows both operands are re-used across tiles, so both go through LDS.  The semantics are
+// those of the 17..128-row path -- the prepass above requantises the rows once per call (e4m3 hi + lo per 32-block), fragment count padded to whole
+// m tiles so that a tile load never leaves the workspace -- and so is the error class: a prefill chunk that crosses 128 rows does not move the logits.
+//   Block: four waves, tile 128 weight rows (n) x BM activation rows (m) x one k-step of 128; a wave owns 64 n x BM / 2 m, four A fragments against
+// BM / 32 B fragment pairs (hi, lo): an A fragment read from LDS feeds 2 x BM / 32 MFMAs.  BM = 128 above 256 rows, 64 up to there (a third m tile
+// of 128 would be mostly padding); K slabs fill the chip where the tiles alone do not.
+//   Stage (one k-step): 8 x 1 KiB of codes, the image's chunks as they are (a lane's 16 bytes are its A operand); 8 x 256 B of scale dwords -- the
+// scale chunk of the k-step's quad, fetched with every k-step of the quad: three of four are L2 hits, and every stage is the same list of loads, so the
+// counted waits are constants; the lane picks byte ks & 3 --; BM / 16 workspace tiles of F4W_TILE bytes, contiguous, copied as they are in 1-KiB
+// wave-instructions (the ragged last one at BM = 64 re-reads the last 16 bytes into padding of the stage).  43 KiB at BM = 128, 27 KiB at BM = 64.
+//   Ring: three stages filled TWO k-steps ahead by LDS-DMA (129 / 81 KiB of the CU's 160: one block per CU -- a k-step is 16-32 MFMAs per wave, the
+// matrix pipe is the bound by an order of magnitude over the 43 KiB of DMA, and a deeper ring covers an L2 round trip where a second block would
+// only halve the ring), counted vmcnt waits, one raw s_barrier per k-step (gemm_fp8_kernel has the reasons).
+//   SwiGLU dual (w / w2): a block's 128 weight rows are 64 gate rows and the 64 up rows of the same columns; a wave holds both for its 32 columns and
+// store4 (or the slab sum) applies SiLU(gate) * up.  Ragged shapes: row groups >= NRG re-read the last group and rows >= N / >= M are never stored;
+// a last k-step beyond K is zero blocks on the x side and zero codes on the w side; the scale chunk of a short last quad is whole in the image.
+//   Tile order: XCD-banded as gemm_fp8_kernel; m fastest (the blocks of a column tile share its codes in one L2) unless the requantised rows are the
+// heavier operand (2.06 x M bytes per k against 0.53 x N), then n fastest.
+#define FP4_GEMM_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(n) : "memory")
+
+template <int BM, bool DUAL>
+__global__ __launch_bounds__(256) void gemm_fp4_kernel(LinArgs a, const char* __restrict__ xq, int tiles_m, int tiles_n, int qps, int n_fast,
+                                                       float* __restrict__ ws, float* __restrict__ ws2) {
+    constexpr int MF = BM / 32;                       // B fragment pairs per wave
+    constexpr int XB = (BM / 16) * F4W_TILE;          // bytes of x per stage
+    constexpr int NI = (XB + 1023) / 1024;            // ... in wave-instructions of 1 KiB
+    constexpr int STAGE = 8192 + 2048 + NI * 1024;
+    constexpr int NXF = NI / 4, EXTRA = NI % 4;       // x instructions per wave: NXF, one more for waves < EXTRA
+    constexpr int LW = 4 + NXF;                       // loads per wave and stage (2 code pieces, 2 scale pieces, x)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g = lane >> 4;
+    const int wn = wave >> 1, wm = wave & 1;
+    int bid = blockIdx.x;
+    {   // XCD-banded tile order (block b runs on XCD b % 8): an XCD works on neighbouring tiles and shares their operands in its L2
+        const int nblk = tiles_m * tiles_n, q = nblk >> 3, r = nblk & 7;
+        const int xcd = bid & 7, idx = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    const int tile_n = n_fast ? bid % tiles_n : bid / tiles_m, tile_m = n_fast ? bid / tiles_n : bid % tiles_m;
+    const int KS = (a.K + 127) >> 7;
+    const int ks0 = blockIdx.y * qps * 4, nks = min(KS, ks0 + qps * 4) - ks0;         // this slab's k-steps (whole quads but the last)
+    const size_t rgb = fp4_rg_bytes(KS);
+
+    // staging sources: wave w brings weight pieces 2w, 2w + 1 (codes and scale dwords) and x instructions w, w + 4, ...
+    const char* wsrc[2];
+    const char* ssrc[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int p = wave * 2 + u;                   // piece p: row group tile_n * 8 + p; DUAL: gate group tile_n * 4 + p, pieces 4..7 the up groups
+        const char* img = (const char*)((DUAL && p >= 4) ? a.w2 : a.w);
+        int rg = DUAL ? tile_n * 4 + (p & 3) : tile_n * 8 + p;
+        if (rg >= a.NRG) rg = a.NRG - 1;
+        wsrc[u] = img + (size_t)rg * rgb + (size_t)ks0 * 1024 + lane * 16;
+        ssrc[u] = img + (size_t)rg * rgb + (size_t)KS * 1024 + lane * 4;
+    }
+    const size_t xstep = (size_t)tiles_m * (BM / 16) * F4W_TILE;                      // the workspace's bytes per k-step
+    const char* const xsrc = xq + (size_t)ks0 * xstep + (size_t)tile_m * XB;
+    int xoff[NXF + 1];
+#pragma unroll
+    for (int p = 0; p <= NXF; ++p) xoff[p] = min(((p * 4 + wave) * 64 + lane) * 16, XB - 16);
+    auto stage = [&](int t, int slot) {
+        char* const sb = smem + slot * STAGE;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            glds16(wsrc[u] + (size_t)t * 1024, sb + (wave * 2 + u) * 1024);
+            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(ssrc[u] + (size_t)((ks0 + t) >> 2) * 256), (lds_ptr_t)(sb + 8192 + (wave * 2 + u) * 256), 4, 0, 0);
+        }
+        const char* const xs = xsrc + (size_t)t * xstep;
+#pragma unroll
+        for (int p = 0; p < NXF; ++p) glds16(xs + xoff[p], sb + 10240 + (p * 4 + wave) * 1024);
+        if (wave < EXTRA) glds16(xs + xoff[NXF], sb + 10240 + (NXF * 4 + wave) * 1024);
+    };
+    f32x4 acc[4][MF];
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf)
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf) acc[nf][mf] = f32x4{0, 0, 0, 0};
+
+    stage(0, 0);
+    if (nks > 1) stage(1, 1);
+    int slot = 0;
+    for (int t = 0; t < nks; ++t) {
+        // this wave's loads of k-step t have landed (those of t + 1 may stay in flight: vmcnt retires in order) ...
+        if (t + 1 < nks) {
+            if (wave < EXTRA) FP4_GEMM_VMWAIT(LW + 1);
+            else FP4_GEMM_VMWAIT(LW);
+        } else {
+            FP4_GEMM_VMWAIT(0);
+        }
+        __builtin_amdgcn_s_barrier();                 // ... everyone's; and every wave is done reading the slot of k-step t - 1
+        asm volatile("" ::: "memory");
+        if (t + 2 < nks) stage(t + 2, slot == 0 ? 2 : slot - 1);
+        const char* const sb = smem + slot * STAGE;
+        const int hb = ((ks0 + t) & 3) * 8;
+        i32x8 bh[MF], bl[MF];
+        int sxh[MF], sxl[MF];
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf) {
+            const char* const xb = sb + 10240 + (wm * MF + mf) * F4W_TILE;
+            const u32x4 h0 = *(const u32x4*)(xb + lane * 16), h1 = *(const u32x4*)(xb + 1024 + lane * 16);
+            const u32x4 l0 = *(const u32x4*)(xb + 2048 + lane * 16), l1 = *(const u32x4*)(xb + 3072 + lane * 16);
+            const uint32_t sx = *(const uint16_t*)(xb + 4096 + lane * 2);
+            bh[mf] = i32x8{(int)h0[0], (int)h0[1], (int)h0[2], (int)h0[3], (int)h1[0], (int)h1[1], (int)h1[2], (int)h1[3]};
+            bl[mf] = i32x8{(int)l0[0], (int)l0[1], (int)l0[2], (int)l0[3], (int)l1[0], (int)l1[1], (int)l1[2], (int)l1[3]};
+            sxh[mf] = (int)(sx & 0xffu); sxl[mf] = (int)(sx >> 8);
+        }
+#pragma unroll
+        for (int nf = 0; nf < 4; ++nf) {
+            const int piece = DUAL ? (nf >> 1) * 4 + wn * 2 + (nf & 1) : wn * 4 + nf;
+            const u32x4 c = *(const u32x4*)(sb + piece * 1024 + lane * 16);
+            const uint32_t sd = *(const uint32_t*)(sb + 8192 + piece * 256 + lane * 4);
+            // cbsz 4: A is e2m1 (its first four registers), blgp 0: B is e4m3; scale bytes in byte 0 of the scale operands
+            const i32x8 af = {(int)c[0], (int)c[1], (int)c[2], (int)c[3], 0, 0, 0, 0};
+            const int sa = (int)((sd >> hb) & 0xffu);
+#pragma unroll
+            for (int mf = 0; mf < MF; ++mf) {
+                acc[nf][mf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bh[mf], acc[nf][mf], 4, 0, 0, sa, 0, sxh[mf]);
+                acc[nf][mf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bl[mf], acc[nf][mf], 4, 0, 0, sa, 0, sxl[mf]);
+            }
+        }
+        slot = slot == 2 ? 0 : slot + 1;
+    }
+
+    // ---- epilogue.  acc[nf][mf]: lane (g, i) holds n = n0 .. n0 + 3 of row m; rows >= M / columns >= N are not stored
+    const int ldw = (a.N + 3) & ~3;
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) {
+        const int m = tile_m * BM + wm * (BM / 2) + mf * 16 + i;
+        if (m >= a.M) continue;
+#pragma unroll
+        for (int nf = 0; nf < (DUAL ? 2 : 4); ++nf) {
+            const int n0 = (DUAL ? tile_n * 4 + wn * 2 + nf : tile_n * 8 + wn * 4 + nf) * 16 + g * 4;
+            if (n0 >= a.N) continue;
+            const f32x4 v = acc[nf][mf], up = acc[DUAL ? nf + 2 : nf][mf];           // (copies: no address of the accumulator array is taken)
+            if (ws) {                                 // K slabs: raw partial sums into slab blockIdx.y, [m][N padded to 4]
+                const size_t o = ((size_t)blockIdx.y * a.M + m) * ldw + n0;
+                *(f32x4*)(ws + o) = v;
+                if (DUAL) *(f32x4*)(ws2 + o) = up;
+            } else {
+                store4(a, m, n0, v, DUAL ? &up : nullptr);
+            }
+        }
+    }
+}
+
+template <int BM>
+static int launch_gemm_fp4_bm(const LinArgs& a, bool xf32, hipStream_t st) {
+    const bool dual = a.w2 != nullptr;
+    const int KS = (a.K + 127) / 128, KQ = (KS + 3) / 4;
+    const int tiles_m = cdiv(a.M, BM), tiles_n = dual ? cdiv(a.NRG, 4) : cdiv(a.NRG, 8);
+    char* xq;
+    if (int rc = requant_rows_fp4(a, xf32, tiles_m * (BM / 16), SM_PROF_GEMM, st, &xq)) return rc;
+    SmProfScope prof(SM_PROF_GEMM, st, ((long long)a.N << 32) | (unsigned)a.K);
+    // K slabs where the tiles do not fill 256 CUs (o and down at a few hundred rows): whole quads, at least two per slab, at most 8 slabs
+    const int blocks = tiles_m * tiles_n;
+    int S = std::max(1, std::min(std::min(8, 256 / blocks), KQ / 2));
+    const int qps = cdiv(KQ, S);
+    S = cdiv(KQ, qps);
+    float *ws = nullptr, *ws2 = nullptr;
+    if (S > 1) {
+        const size_t slab = (size_t)S * a.M * ((a.N + 3) & ~3);
+        int rc = splitk_workspace(st, slab * sizeof(float) * (dual ? 2 : 1), &ws);
+        if (rc) return rc;
+        if (dual) ws2 = ws + slab;
+    }
+    constexpr int sh = 3 * (8192 + 2048 + (((BM / 16) * F4W_TILE + 1023) / 1024) * 1024);
+    {   // (above the default limit of 64 KiB; a function attribute is per device: set once on each)
+        static std::mutex mu;
+        static bool attr_set[64] = {};
+        int dev = 0;
+        SM_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+            SM_HIP(hipFuncSetAttribute((const void*)gemm_fp4_kernel<BM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, sh));
+            SM_HIP(hipFuncSetAttribute((const void*)gemm_fp4_kernel<BM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sh));
+            if (dev >= 0 && dev < 64) attr_set[dev] = true;
+        }
+    }
+    const int n_fast = (long)tiles_m * BM * 4 > (long)a.N * (dual ? 2 : 1);          // 2.06 x M against 0.53 x N bytes per k
+    const dim3 grid(blocks, S);
+    if (dual) gemm_fp4_kernel<BM, true><<<grid, 256, sh, st>>>(a, xq, tiles_m, tiles_n, qps, n_fast, ws, ws2);
+    else gemm_fp4_kernel<BM, false><<<grid, 256, sh, st>>>(a, xq, tiles_m, tiles_n, qps, n_fast, ws, ws2);
+    SM_LAUNCH_CHECK();
+    if (S == 1) return SM_OK;
+    return launch_splitk_reduce(a, ws, S, (a.N + 3) & ~3, st, ws2);
+}
+
+// sm_linear with SM_W_FP4_GEMM above 128 rows (linear.hip validated the call)
+int launch_gemm_fp4(const LinArgs& a, bool xf32, hipStream_t st) {
+    if (a.M > 256) return launch_gemm_fp4_bm<128>(a, xf32, st);
+    return launch_gemm_fp4_bm<64>(a, xf32, st);
 }

@@ -121,6 +121,7 @@ int sm_sample_rows_tab(const float* logits, int S, int V, int ld, const SmSample
 
 // Optional in-library kernel timing (bench.py's roofline leg): when a class bit is enabled, every launch of that
 // class is bracketed by HIP events recorded ON THE LAUNCH STREAM; sm_prof_read() synchronises and sums.
+int sm_fp4_gemm_max_rows();      // linear.hip: the last row count at which SM_W_FP4_GEMM takes the tiled fp4 GEMM (above: the expansion, as SM_W_FP4_MFMA)
 enum { SM_PROF_GEMM = 0, SM_PROF_SKINNY = 1, SM_PROF_ATTN = 2, SM_PROF_NCLS = 3 };
 void sm_prof_begin_(int cls, hipStream_t st, long long tag);
 void sm_prof_end_(int cls, hipStream_t st);

@@ -1682,8 +1682,31 @@ static bool fp4_wstream_takes(const sm_linear_t* p) {
            (p->ldx % (xf32 ? 4 : 8)) == 0 && ((uintptr_t)p->x & 15) == 0;
 }
 
+// SM_W_FP4_GEMM at FP4_GEMM_MIN_ROWS < M <= FP4_GEMM_MAX_ROWS: the prepass + tiled kernel of gemm_fp4.hip (it carries what the weight stream carries).  Every
+// other SM_W_FP4_GEMM call is SM_W_FP4_MFMA exactly: its kernels up to 128 rows, the expansion above.  SM_FP4_GEMM=0: never the tiled kernel (A/B)
+// The upper bound is measured (tools/decode_bench.py --fp4-prefill with a list of lengths, Mistral-7B shapes, one run on one box, ms per prefill, expansion
+// against the tiled kernel): 129 rows 9.52 / 7.16, 256: 10.58 / 8.20, 328: 11.18 / 10.95, 512: 12.92 / 12.63, 640: 17.09 / 17.09, 768: 18.48 / 19.94, 1024: 19.84 / 21.80,
+// 2048: 30.64 / 40.77 (spread below 0.05 ms everywhere) -- hi + lo is two matrix steps per weight fragment, and beyond 512 rows that costs more than the expansion
+#define FP4_GEMM_MIN_ROWS 128
+#define FP4_GEMM_MAX_ROWS 512
+int sm_fp4_gemm_max_rows() { return FP4_GEMM_MAX_ROWS; }      // (host.h: the model peels post-norms off SM_W_FP4_GEMM products up to here)
+static bool fp4_gemm_takes(const sm_linear_t* p) {
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("SM_FP4_GEMM"); on = e ? atoi(e) : 1; }
+    const bool xf32 = p->x_dtype == SM_X_F32;
+    if (p->act == SM_ACT_SWIGLU_DUAL && (p->bias || ((p->N >> 1) & 15) || p->w2)) return false;      // (the w / w2 form pairs whole row groups and has one bias)
+    return on && p->w_dtype == SM_W_FP4_GEMM && p->M > FP4_GEMM_MIN_ROWS && p->M <= FP4_GEMM_MAX_ROWS && p->op_dtype == SM_OP_BF16 && !p->vt && p->remap_in == 0 && p->x_rep <= 1 && !p->precise &&
+           !p->norm_gamma && !p->post_ln_gamma && !p->fold_stats_in && !p->fold_stats_out && !p->tile_hint && (p->K & 31) == 0 && p->ldx >= p->K &&
+           (p->ldx % (xf32 ? 4 : 8)) == 0 && ((uintptr_t)p->x & 15) == 0;
+}
+
 extern "C" int sm_linear(const sm_linear_t* p, void* stream) {
     SM_REQUIRE(p, "sm_linear: null args");
+    if (p->w_dtype == SM_W_FP4_GEMM && !fp4_gemm_takes(p)) {
+        sm_linear_t q = *p;
+        q.w_dtype = SM_W_FP4_MFMA;
+        return sm_linear(&q, stream);
+    }
     if (const int m1 = rowsplit_rows(p)) {
         sm_linear_t a = *p, b = *p;
         a.M = m1;
@@ -1698,8 +1721,8 @@ extern "C" int sm_linear(const sm_linear_t* p, void* stream) {
         SM_REQUIRE(p->M > 16 && p->x_dtype == SM_X_BF16 && p->out_bf16 && !p->out_f32 && !p->residual && !p->vt && !p->w2 && p->remap_in == 0 && !p->post_ln_gamma &&
                    !p->norm_gamma && (p->N & 1) == 0 && p->ldo_bf16 >= F,
                    "sm_linear: SM_ACT_SWIGLU_DUAL needs M > 16, 16-bit x, one [gate | up] weight image (N even) and a 16-bit output [M][ldo_bf16 >= N / 2] only");
-        if (fp4_wstream_takes(p) && !p->bias && (F & 15) == 0) {
-            // the fp4 weight stream pairs the gate and the up group of a column in one wave: the [gate | up] image as w and w2 (a fused image is the
+        if (p->w_dtype == SM_W_FP4_GEMM || (fp4_wstream_takes(p) && !p->bias && (F & 15) == 0)) {
+            // the fp4 weight stream and the tiled fp4 GEMM pair the gate and the up group of a column in one wave: the [gate | up] image as w and w2 (a fused image is the
             // concatenation of its parts' row groups)
             sm_linear_t q = *p;
             q.act = SM_ACT_NONE; q.N = F;
@@ -1779,12 +1802,13 @@ static int linear_impl(const sm_linear_t* p, void* stream, bool* ln_done) {
     const bool lds64 = (sm_skinny_lds64_on() >= 2 || (sm_skinny_lds64_on() == 1 && w8_any)) && p->M > 32 && p->M <= 64 && p->x_dtype == SM_X_BF16 && !p->precise && !p->norm_gamma && ((p->N & 3) == 0 || p->N < 4) && a.KS >= 8 &&
                        p->remap_in == 0 && !p->vt && (p->ldx % 8) == 0 && p->act != SM_ACT_SWIGLU_DUAL;
     const bool f4w = fp4_wstream_takes(p) && p->act != SM_ACT_SWIGLU_DUAL;
-    SM_REQUIRE(!p->w2 || p->M <= 32 || lds64 || f4w, "sm_linear: dual weights only on the weight-streaming path (M <= 32; 16-bit rows up to 64)");
+    const bool f4g = p->w_dtype == SM_W_FP4_GEMM;                // (sm_linear let it through: the tiled fp4 GEMM takes the call)
+    SM_REQUIRE(!p->w2 || p->M <= 32 || lds64 || f4w || f4g, "sm_linear: dual weights only on the weight-streaming path (M <= 32; 16-bit rows up to 64)");
     SM_REQUIRE(p->x_rep > 1 || p->ldx >= a.KS * 32, "sm_linear: ldx=%d must cover K padded to 32 (%d)", p->ldx, a.KS * 32);
     SM_REQUIRE(!p->vt || (p->vt_dh > 0 && p->vt_S > 0 && (p->N - p->vt_n0) % p->vt_dh == 0), "sm_linear: bad vt args");
     hipStream_t st = (hipStream_t)stream;
     const bool xf32 = p->x_dtype == SM_X_F32;
-    if (p->w_dtype == SM_W_FP4 || p->w_dtype == SM_W_FP4_MFMA) {
+    if (p->w_dtype == SM_W_FP4 || p->w_dtype == SM_W_FP4_MFMA || f4g) {
         // MXFP4 weights (gemm_fp4.hip).  Up to 16 rows: the block-scaled MFMA weight stream; what that kernel does not do is refused, never
         // replaced by a different product.  More rows: the image is expanded to a packed bf16 scratch and the bf16 kernels below run on it.
         SM_REQUIRE(p->op_dtype == SM_OP_BF16, "sm_linear: fp4 weights take bf16 operands (op_dtype SM_OP_F16 is not supported)");
@@ -1798,9 +1822,13 @@ static int linear_impl(const sm_linear_t* p, void* stream, bool* ln_done) {
             return launch_skinny_fp4(a, xf32, st);
         }
         if (f4w) return launch_wstream_fp4(a, xf32, st);      // SM_W_FP4_MFMA, 17..128 rows: x requantised once, one pass over the codes
+        if (f4g) return launch_gemm_fp4(a, xf32, st);         // SM_W_FP4_GEMM, 129..512 rows: the same prepass, the tiled kernel
         const void *d0 = nullptr, *d1 = nullptr;
-        int rc = dequant_fp4(st, 0, p->w, p->N, p->K, &d0);
-        if (!rc && p->w2) rc = dequant_fp4(st, 1, p->w2, p->N, p->K, &d1);
+        int rc;
+        {   SmProfScope prof(SM_PROF_GEMM, st, (1LL << 61) | ((long long)p->N << 32) | (unsigned)p->K);      // (tag of the expansion launches: tools/decode_bench.py --fp4-prefill)
+            rc = dequant_fp4(st, 0, p->w, p->N, p->K, &d0);
+            if (!rc && p->w2) rc = dequant_fp4(st, 1, p->w2, p->N, p->K, &d1);
+        }
         if (rc) return rc;
         a.w = (const bf16x8*)d0;
         if (p->w2) a.w2 = (const bf16x8*)d1;

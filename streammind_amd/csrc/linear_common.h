@@ -142,5 +142,6 @@ int launch_splitk_reduce(const LinArgs& a, const float* ws, int S, int ldw, hipS
 int launch_skinny_fp4(const LinArgs& a, bool xf32, hipStream_t st);          // gemm_fp4.hip (MXFP4 weights, <= 16 rows: block-scaled MFMA, x requantised to e4m3 hi + lo)
 int launch_dequant_fp4(const void* w4, int N, int K, void* dst_packed_bf16, hipStream_t st);     // gemm_fp4.hip (fp4 image -> packed bf16 image, for more rows)
 int launch_wstream_fp4(const LinArgs& a, bool xf32, hipStream_t st);         // gemm_fp4.hip (SM_W_FP4_MFMA, 17..128 rows: x requantised once into a workspace, the codes streamed through register rings)
+int launch_gemm_fp4(const LinArgs& a, bool xf32, hipStream_t st);            // gemm_fp4.hip (SM_W_FP4_GEMM above 128 rows: the same prepass, codes and requantised rows tiled through an LDS ring)
 void release_fp4_workspace(hipStream_t st);                                 // gemm_fp4.hip: ... that workspace
 void release_stream_workspaces(hipStream_t st);                           // linear.hip: free the per-stream slabs of a stream about to be destroyed

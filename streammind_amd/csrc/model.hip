@@ -134,6 +134,7 @@ struct Slot {            // one tensor the path reads
 struct sm_model {
     sm_config_t c;
     int weights_fp4 = 0;           // sm_model_set_weights_fp4's mode: 0 off, 1 SM_W_FP4, 2 SM_W_FP4_MFMA (not part of sm_config_t: the struct is ABI)
+    bool fp4_gemm = false;         // sm_model_set_fp4_gemm: mode 2's slots go out as SM_W_FP4_GEMM (the tiled fp4 GEMM above 128 rows)
     bool any_loaded = false;       // a tensor has been handed over: the weight formats are fixed from here on
     std::unordered_map<std::string, Slot> slots;           // canonical name -> storage
     struct Route { std::string slot; int row0; int rows; int part; };   // checkpoint name -> (slot, first row, row count, index of this part)
@@ -608,15 +609,25 @@ extern "C" int sm_model_set_weights_fp4(sm_model* m, int on) {
     SM_REQUIRE(!on || m->c.llm_layers == 0 || ((m->c.llm_hidden & 31) == 0 && (m->c.llm_mlp & 31) == 0), "sm_model_set_weights_fp4: llm_hidden and llm_mlp must be multiples of 32");
     SM_REQUIRE(on >= 0 && on <= 2, "sm_model_set_weights_fp4: mode %d (0 off, 1 expansion above 16 rows, 2 the fp4 weight stream up to 128 rows)", on);
     m->weights_fp4 = on;
+    if (on != 2) m->fp4_gemm = false;
     for (auto& kv : m->slots)
         if (kv.second.kind == 1 && kv.first.rfind("llm.model.layers.", 0) == 0) kv.second.fp4 = on != 0;
     return SM_OK;
 }
+// mode 2 only: prefill chunks above 128 rows on the tiled fp4 GEMM (SM_W_FP4_GEMM) instead of the per-call expansion.  Same window as the setter above.
+extern "C" int sm_model_set_fp4_gemm(sm_model* m, int on) {
+    SM_REQUIRE(m && !m->any_loaded && !m->finalized, "sm_model_set_fp4_gemm: call it between sm_model_create and the first sm_model_load_tensor");
+    SM_REQUIRE(on == 0 || on == 1, "sm_model_set_fp4_gemm: on = %d (0 or 1)", on);
+    SM_REQUIRE(!on || m->weights_fp4 == 2, "sm_model_set_fp4_gemm: needs sm_model_set_weights_fp4(m, 2) first");
+    m->fp4_gemm = on != 0;
+    return SM_OK;
+}
 extern "C" int sm_norm_ex(const float* x, int M, int D, int ldx, const float* gamma, const float* beta, float eps, int post_act,
                           float* out_f32, void* out_bf16, int ldo, int op_dtype, void* stream);
-// sm_linear; where the product's kernel does not carry the norm of the finished rows (fp4 weights up to 16 rows, SM_W_FP4_MFMA up to 128) the norm is the launch behind it
+// sm_linear; where the product's kernel does not carry the norm of the finished rows (fp4 weights up to 16 rows, SM_W_FP4_MFMA up to 128, SM_W_FP4_GEMM up to
+// the last row count its tiled kernel takes: above that the expansion's slab sum carries the norm, as in mode 2) the norm is the launch behind it
 static int linear_post_norm(const sm_linear_t& a, void* stream) {
-    const bool peel = (a.w_dtype == SM_W_FP4 && a.M <= 16) || (a.w_dtype == SM_W_FP4_MFMA && a.M <= 128);
+    const bool peel = (a.w_dtype == SM_W_FP4 && a.M <= 16) || (a.w_dtype == SM_W_FP4_MFMA && a.M <= 128) || (a.w_dtype == SM_W_FP4_GEMM && a.M <= sm_fp4_gemm_max_rows());
     if (!peel || !a.post_ln_gamma) return sm_linear(&a, stream);
     sm_linear_t b = a;
     b.post_ln_gamma = nullptr; b.post_ln_out = nullptr; b.post_ln_out_f32 = nullptr;
@@ -630,7 +641,7 @@ static sm_linear_t lin(const sm_model* m, const Slot& w, const void* x, int x_dt
     sm_linear_t a;
     memset(&a, 0, sizeof(a));
     a.w = w.buf.p; a.N = w.N; a.K = w.K; a.x = x; a.x_dtype = x_dtype; a.M = M; a.ldx = ldx;
-    if (w.fp4) a.w_dtype = m->weights_fp4 == 2 ? SM_W_FP4_MFMA : SM_W_FP4;
+    if (w.fp4) a.w_dtype = m->weights_fp4 == 2 ? (m->fp4_gemm ? SM_W_FP4_GEMM : SM_W_FP4_MFMA) : SM_W_FP4;
     if (w.fp8) { a.w_dtype = m->c.weights_fp8 == 2 && !w.wo ? SM_W_FP8_MFMA : SM_W_FP8; a.w_scale = w.scale.as<float>(); }
     if (w.f16) a.op_dtype = SM_OP_F16;
     return a;

@@ -62,6 +62,7 @@ class PathConfig:
                                    # and calls with > 16 rows run fp8 x fp8 MFMA on per-row-quantised activations (gemm_fp8.hip)
     weights_fp4: int = 0           # opt-in: the LLM's q|k|v, o, gate|up, down as MXFP4 images (sm_model_set_weights_fp4; exclusive with weights_fp8 / llm_fp16).
                                    # the setter's mode: True / 1 = expansion above 16 rows, 2 = the fp4 weight stream up to 128 rows (group decode up to 128 streams)
+    fp4_gemm: bool = False         # opt-in, needs weights_fp4 = 2: prefill chunks above 128 rows on the tiled fp4 GEMM instead of the per-call expansion (sm_model_set_fp4_gemm)
     vit_fp16: bool = False         # vision-tower operands in IEEE fp16 (the reference demo's precision) instead of bf16
     llm_fp16: bool = False         # the same for the LLM (weights, embedding table, activations, q / KV caches, attention P)
     proj_fp16: bool = False        # the same for the connector + gate weights (activations as fp16 hi/lo pairs in precise mode)
@@ -120,6 +121,8 @@ class NativeModel:
         self.h = h
         if getattr(cfg, "weights_fp4", False):       # not a field of sm_config_t (the struct is ABI): a setter, before the first tensor
             check(self.lib.sm_model_set_weights_fp4(self.h, int(cfg.weights_fp4)), "sm_model_set_weights_fp4")
+        if getattr(cfg, "fp4_gemm", False):
+            check(self.lib.sm_model_set_fp4_gemm(self.h, 1), "sm_model_set_fp4_gemm")
         self.finalized = False
         self.ignored = []
 
@@ -532,7 +535,8 @@ def linear(x: torch.Tensor, wp: torch.Tensor, N: int, K: int, *, w2p: Optional[t
     the same call (sm_linear_t.post_ln_*), post_ln_act applied to the normalised value; x_rep = (rep, dh): x holds K / rep columns and column
     group j of width dh is read rep times (the gate's repeat_kv in front of o_proj).
     fp8_mfma (with w_scale): SM_W_FP8_MFMA -- above 16 rows the activations are quantised per row and the product is fp8 x fp8.
-    w_fp4: wp (and w2p) are MXFP4 images (pack_weight_fp4): True / 1 = SM_W_FP4, 2 = SM_W_FP4_MFMA (17..128 rows on the fp4 weight stream)."""
+    w_fp4: wp (and w2p) are MXFP4 images (pack_weight_fp4): True / 1 = SM_W_FP4, 2 = SM_W_FP4_MFMA (17..128 rows on the fp4 weight stream),
+    3 = SM_W_FP4_GEMM (as 2, and more than 128 rows on the tiled fp4 GEMM)."""
     lib = _lib.load()
     assert x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.dtype in (torch.bfloat16, torch.float32, torch.float16)
     if x.dtype == torch.float16:       # fp16 operands: `wp` must be the packed image of fp16 weights (pack_weight moves 16-bit words)
@@ -554,7 +558,7 @@ def linear(x: torch.Tensor, wp: torch.Tensor, N: int, K: int, *, w2p: Optional[t
         a.w_dtype, a.w_scale, a.w2_scale = (_lib.SM_W_FP8_MFMA if fp8_mfma else _lib.SM_W_FP8), w_scale.data_ptr(), _p(w2_scale)
     if w_fp4:
         assert w_scale is None, "an MXFP4 image carries its scales"
-        a.w_dtype = _lib.SM_W_FP4_MFMA if int(w_fp4) == 2 else _lib.SM_W_FP4
+        a.w_dtype = {2: _lib.SM_W_FP4_MFMA, 3: _lib.SM_W_FP4_GEMM}.get(int(w_fp4), _lib.SM_W_FP4)
     if residual is not None:
         a.residual, a.ldr = residual.data_ptr(), residual.shape[1]
     if norm_gamma is not None:

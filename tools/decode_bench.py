@@ -4,7 +4,10 @@ fraction of the HBM roof on each format's own bytes per token, the summed HIP-ev
 product shape (us per launch, TB/s on the product's own weight bytes), and ms per batched decode step at 4 / 8 / 16 streams; then the wide groups.
 --fp4-groups: only the wide groups -- batched decode at 32 / 64 / 128 streams on bf16, fp8 (32, 64: its cap) and MXFP4 mode 2 (weights_fp4=2: the fp4
 weight stream of 17..128 rows), the formats alternating over three rounds (median ms per step), and for fp4 the HIP-event time of every product of a
-layer (us per launch incl. its slab sum, TB/s on the product's own 4.25-bit bytes) and of the activation prepass launches (their share of a step)."""
+layer (us per launch incl. its slab sum, TB/s on the product's own 4.25-bit bytes) and of the activation prepass launches (their share of a step).
+--fp4-prefill: prefills of 328 and 2048 tokens on bf16, MXFP4 mode 2 (the per-call expansion above 128 rows) and mode 2 + fp4_gemm (the tiled fp4 GEMM),
+the three alternating over three rounds in one process (median ms per prefill, min..max), and per product of a layer the HIP-event us per launch
+(expansion leg: the product and, apart, the expansion launches in front of it; fp4_gemm leg: the product incl. its slab sum, and the prepass launches)."""
 import ctypes as C
 import json, os, statistics, sys, time
 import torch
@@ -102,6 +105,62 @@ def three_formats(n_new):
     wide_groups()
 
 
+def fp4_prefill(rounds=3, lengths=(328, 2048)):
+    legs = {name: make_model(**kw) for name, kw in (("bf16", {}), ("fp4_expand", dict(weights_fp4=2)), ("fp4_gemm", dict(weights_fp4=2, fp4_gemm=True)))}
+    g = torch.Generator(device="cuda").manual_seed(17)
+    ids = {n: torch.randint(3, 32000, (n,), generator=g, device="cuda", dtype=torch.int32) for n in lengths}
+    streams = {name: m.open_stream(max_frames=8, max_seq=max(lengths)) for name, (cfg, m) in legs.items()}
+
+    def run(name, n, reps):
+        st = streams[name]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            st.set_kv_len(0); st.prefill(ids[n])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / reps
+
+    for name in legs:                                                           # every shape warmed before it is timed
+        for n in lengths:
+            run(name, n, 2)
+    ms = {name: {n: [] for n in lengths} for name in legs}
+    for _ in range(rounds):                                                     # alternate: a drifting box hits every leg alike
+        for name in legs:
+            for n in lengths:
+                ms[name][n].append(run(name, n, 8 if n <= 512 else 3))
+    out = {name: {n: {"ms_per_prefill": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for n, v in per.items()} for name, per in ms.items()}
+    products = (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    for name, (cfg, m) in legs.items():                                         # HIP events around every product launch of two prefills (class 0: the tiled products)
+        for n in lengths:
+            m.lib.sm_prof_reset(); m.lib.sm_prof_enable(1 << 0)
+            run(name, n, 2)
+            m.lib.sm_prof_enable(0)
+
+            def read(tag):
+                c2, m2 = C.c_int(), C.c_float()
+                m.lib.sm_prof_read_tag(0, C.c_longlong(tag), C.byref(c2), C.byref(m2))
+                return (c2.value, round(m2.value * 1e3 / c2.value, 2)) if c2.value else (0, None)
+            per = {}
+            for label, N, K in products:
+                cnt, us = read((N << 32) | K)
+                if not cnt and label == "gate_up":                              # (the tiled fp4 GEMM runs gate | up in its w / w2 form: N = 14336)
+                    cnt, us = read(((N // 2) << 32) | K)
+                per[label] = {"launches": cnt, "us": us}
+                ecnt, eus = read((1 << 61) | (N << 32) | K)
+                if ecnt:
+                    per[label]["expansion_us"] = eus
+            for K in (4096, 14336):
+                cnt, us = read((1 << 62) | K)
+                if cnt:
+                    per["prepass_k%d" % K] = {"launches": cnt, "us": us}
+            out[name][n]["per_product"] = per
+    print(json.dumps({"fp4_prefill": out}))
+
+
+if "--fp4-prefill" in sys.argv:                                                 # [lengths, comma-separated: a scan for the dispatch's row bound]
+    i = sys.argv.index("--fp4-prefill")
+    fp4_prefill(lengths=tuple(int(v) for v in sys.argv[i + 1].split(",")) if len(sys.argv) > i + 1 else (328, 2048))
+    sys.exit(0)
 if "--fp4-groups" in sys.argv:
     wide_groups()
     sys.exit(0)
