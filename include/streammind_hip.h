@@ -403,6 +403,10 @@ int sm_set_vit_ln_fold(int mode);
  * 128 x 128 tiles on this chip (8..10 and 15..20 frames of 577 tokens on 256 CUs) runs as TWO half batches on two HIP streams -- 4-9 % less time per call, results those
  * of the two half calls --, 1 = never, 2..8 = that many lanes for calls of up to SM_VIT_SMALL_MAX (8) frames, -2 = back to SM_VIT_SMALL_LANES / the default. */
 int sm_set_vit_frame_lanes(int mode);
+/* The fp32 + residual epilogue of the one-tile 256 x 256 kernel (process-wide): 1 = the default, the residual rows are requested ahead of the passes
+ * that write them (the first ones before the accumulators are staged), 0 = the earlier epilogue, -1 = back to the SM_GEMM_EPILOGUE environment variable /
+ * the default.  Results are bit-identical for every value: an A/B and test switch. */
+int sm_set_gemm_epilogue(int mode);
 /* the same from normalised pixel_values [B][3][H][W] (what the reference's callers hand to CLIPVisionTower.forward) */
 int sm_vit_encode_pixels(sm_model* m, const void* pixel_values, int dtype, int B, float* pooled, void* feats_bf16_opt,
                          void* stream);

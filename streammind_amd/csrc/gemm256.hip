@@ -19,6 +19,7 @@
 // CU -- one block per CU walks its tiles and keeps the LDS-DMA pipeline running across the seam between two tiles (in situ: fc1
 // 138 -> 125 us, QKV 96 -> 87 us on the same box; bit-identical results).
 #include <stdlib.h>
+#include <atomic>
 #include <type_traits>
 
 #include "linear_common.h"
@@ -43,6 +44,24 @@ __device__ long long* g_gemm_timeline;
 #else
 #define TL(k) do {} while (0)
 #endif
+
+// The fp32 + residual epilogue of the one-tile 256 x 256 kernel, process-wide (sm_set_gemm_epilogue / SM_GEMM_EPILOGUE): 1 = the residual rows are requested ahead of
+// the passes that write them (gemm256_kernel<.., EPI2 = true>), 0 = half_rows_epilogue as it was (A/B, tests); results are bit-identical either way.
+static std::atomic<int> g_gemm_epilogue{-1};          // -1 = read SM_GEMM_EPILOGUE (default 1)
+extern "C" int sm_set_gemm_epilogue(int mode) {
+    SM_REQUIRE(mode >= -1 && mode <= 1, "sm_set_gemm_epilogue: -1 (environment / default), 0 (the earlier epilogue), 1 (residual prefetch); got %d", mode);
+    g_gemm_epilogue.store(mode, std::memory_order_relaxed);
+    return SM_OK;
+}
+static int gemm_epilogue_mode() {
+    int m = g_gemm_epilogue.load(std::memory_order_relaxed);
+    if (m < 0) {
+        const char* e = getenv("SM_GEMM_EPILOGUE");
+        m = e ? (atoi(e) != 0) : 1;
+        g_gemm_epilogue.store(m, std::memory_order_relaxed);
+    }
+    return m;
+}
 
 template <int ACT, int CPR, int RPP, bool F16>     // CPR: 16-byte chunks per staged row; RPP: rows covered by one pass of the block
 __device__ __forceinline__ void half_rows_epilogue(const char* __restrict__ smem, const float* __restrict__ bias,
@@ -155,7 +174,7 @@ __device__ __forceinline__ void half_rows_epilogue_fold(const char* __restrict__
     }
 }
 
-template <int ACT, int WN, bool F16, bool PFOLD = false>   // WN = wave columns along n: tile is 256(m) x 128*WN(n), 4*WN waves; F16: fp16 operands / outputs; PFOLD: producer of a folded LayerNorm (its own instantiation: inlined beside the plain epilogue it cost that kernel 192 bytes of scratch)
+template <int ACT, int WN, bool F16, bool PFOLD = false, bool EPI2 = false>   // EPI2 (256 x 256 tile): the residual-prefetching fp32 epilogue of sm_set_gemm_epilogue; WN = wave columns along n: tile is 256(m) x 128*WN(n), 4*WN waves; F16: fp16 operands / outputs; PFOLD: producer of a folded LayerNorm (its own instantiation: inlined beside the plain epilogue it cost that kernel 192 bytes of scratch)
 __global__ __launch_bounds__(256 * WN, 2) void gemm256_kernel(LinArgs a, int tiles_m, int tiles_n, int cb) {
     constexpr int BN = 128 * WN;
     constexpr int NW = 4 * WN;                       // waves
@@ -610,9 +629,7 @@ __global__ __launch_bounds__(256 * WN, 2) void gemm256_kernel(LinArgs a, int til
             return;
         }
     }
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if (half) { __syncthreads(); TL(3); }
+    auto stage_half = [&](int half) {
         if ((wm >> 1) == half) {
 #pragma unroll
             for (int p = 0; p < NP; ++p)
@@ -623,6 +640,73 @@ __global__ __launch_bounds__(256 * WN, 2) void gemm256_kernel(LinArgs a, int til
                     *(f32x4*)(smem + ml * ROWB + ((chunk ^ (ml & 31)) * 16)) = piece(p, mb);
                 }
         }
+    };
+    if constexpr (WN == 2 && EPI2 && !PFOLD && ACT >= 0) {
+        // fp32 + residual outputs (out-proj, fc2) with the residual read taken off the critical path.  The residual does not depend on the
+        // accumulators: the tile's 32 passes (8 rows each: a wave reads and writes one whole 1-KiB row per pass) are one sequence across both
+        // halves, and the residual rows of pass q + AHEAD are requested when pass q is written -- the first AHEAD passes here, before the
+        // accumulators are staged, so that their flight covers the staging and the barrier.  The earlier form (half_rows_epilogue) requests four
+        // rows, waits for them and writes them, 8 dependent HBM round trips per tile with all 256 CUs at the same point.
+        // AHEAD = 8 (32 registers beside the 128 accumulators of the waves that stage second: 246 VGPRs, no scratch; 16 spills): the write-through
+        // stores are asm the compiler's counted waits do not see, so its vmcnt(AHEAD - 1) in front of pass q also waits for the stores of the passes
+        // up to about q - AHEAD / 2 -- the effective distance is half the nominal one.
+        // Rows >= M are clamped to row M - 1 (read, never used); a lane reads the element it later writes, so residual == out_f32 is safe.
+        if (fast && !vt_tile && a.residual) {
+            constexpr int AHEAD = 8, NQ = 256 / RPP, HQ = 128 / RPP;
+            const int chunk = tid % CPR, rsub = tid / CPR;
+            const int n = tile_n * BN + chunk * 4;
+            const int mt = tile_m * G2_BM + rsub;
+            const float* const __restrict__ rp = a.residual + n;
+            float* const __restrict__ of = a.out_f32;
+            bf16_t* const __restrict__ ob = a.out_bf16;
+            auto rload = [&](int q) {
+                int m = mt + q * RPP;
+                if (m >= a.M) m = a.M - 1;
+                return *(const f32x4*)(rp + (size_t)m * a.ldr);
+            };
+            f32x4 b4 = {0, 0, 0, 0};
+            if (a.bias) b4 = *(const f32x4*)(a.bias + n);
+            f32x4 r[AHEAD];
+#pragma unroll
+            for (int q = 0; q < AHEAD; ++q) r[q] = rload(q);
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                if (half) { __syncthreads(); TL(3); }
+                stage_half(half);
+                __syncthreads();
+                auto vload = [&](int p) {
+                    const int ml = p * RPP + rsub;
+                    return *(const f32x4*)(smem + ml * ROWB + ((chunk ^ (ml & 31)) * 16));
+                };
+                f32x4 vn = vload(0);
+#pragma unroll
+                for (int p = 0; p < HQ; ++p) {
+                    const int q = half * HQ + p;
+                    const f32x4 v = vn;
+                    if (p + 1 < HQ) vn = vload(p + 1);         // (the stores below are asm with a memory clobber: the next pass's LDS read would not be moved above them)
+                    const int m = mt + q * RPP;
+                    f32x4 o;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float t = v[j] + b4[j];
+                        if (ACT == SM_ACT_QUICK_GELU) t = t * sigmoidf_(1.702f * t);
+                        o[j] = t + r[q % AHEAD][j];
+                    }
+                    if (m < a.M) {
+                        if (of) store16_wt(of + (size_t)m * a.ldo + n, __builtin_bit_cast(u32x4, o));
+                        if (ob) *(u32x2*)(ob + (size_t)m * a.ldo_bf16 + n) = u32x2{pack16<F16>(o[0], o[1]), pack16<F16>(o[2], o[3])};
+                    }
+                    if (q + AHEAD < NQ) r[q % AHEAD] = rload(q + AHEAD);
+                }
+            }
+            TL(4);
+            return;
+        }
+    }
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        if (half) { __syncthreads(); TL(3); }
+        stage_half(half);
         __syncthreads();
         const int m0 = tile_m * G2_BM + half * 128;
         if (vt_tile) {
@@ -984,7 +1068,11 @@ static int launch_wn(const LinArgs& a, int act, hipStream_t st, bool allow_persi
         SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<0, WN, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<1, WN, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<-1, WN, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        if constexpr (WN == 2) SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<0, WN, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        if constexpr (WN == 2) {
+            SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<0, WN, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+            SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<0, WN, F16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+            SM_HIP(hipFuncSetAttribute((const void*)gemm256_kernel<1, WN, F16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        }
         attr_set = true;
     }
     const dim3 grid(tiles_m * tiles_n, S);              // S > 1 (WN == 2, one-tile kernel only): split-K slabs, see the kernel
@@ -1048,6 +1136,15 @@ static int launch_wn(const LinArgs& a, int act, hipStream_t st, bool allow_persi
             SM_LAUNCH_CHECK();
             return SM_OK;
         } else return SM_EINVAL;
+    }
+    if constexpr (WN == 2) {
+        // a launch with a residual takes the prefetching epilogue (sm_set_gemm_epilogue)
+        if (S == 1 && a.residual && (act == SM_ACT_NONE || act == SM_ACT_QUICK_GELU) && gemm_epilogue_mode()) {
+            if (act == SM_ACT_NONE) gemm256_kernel<0, WN, F16, false, true><<<grid, 256 * WN, LDS, st>>>(a, tiles_m, tiles_n, cb);
+            else gemm256_kernel<1, WN, F16, false, true><<<grid, 256 * WN, LDS, st>>>(a, tiles_m, tiles_n, cb);
+            SM_LAUNCH_CHECK();
+            return SM_OK;
+        }
     }
     if (act == SM_ACT_NONE) gemm256_kernel<0, WN, F16><<<grid, 256 * WN, LDS, st>>>(a, tiles_m, tiles_n, cb);
     else if (act == SM_ACT_QUICK_GELU) gemm256_kernel<1, WN, F16><<<grid, 256 * WN, LDS, st>>>(a, tiles_m, tiles_n, cb);

@@ -502,6 +502,11 @@ def set_vit_frame_lanes(mode: int) -> None:
     check(_lib.load().sm_set_vit_frame_lanes(int(mode)), "sm_set_vit_frame_lanes")
 
 
+def set_gemm_epilogue(mode: int) -> None:
+    """fp32 + residual epilogue of the one-tile 256 x 256 kernel, process-wide (sm_set_gemm_epilogue): 1 residual prefetch (the default), 0 the earlier epilogue, -1 environment / default; bit-identical results"""
+    check(_lib.load().sm_set_gemm_epilogue(int(mode)), "sm_set_gemm_epilogue")
+
+
 def set_prefill_attention_kernel(on: int) -> None:
     """which kernel runs the causal prefill at head_dim 128 (sm_set_prefill_attention_kernel): 1 the prefill kernel, 0 the general tile kernel, -1 environment / default"""
     check(_lib.load().sm_set_prefill_attention_kernel(int(on)), "sm_set_prefill_attention_kernel")
