@@ -288,6 +288,27 @@ int sm_llm_decode_attention_window(const void* q, const void* kcache, const void
                                    float* workspace, int splits_max, void* ctx, void* stream);
 int sm_llm_decode_attention(const void* q_bf16, const void* kcache, const void* vtcache, int pos, int H, int KV, int dh,
                             int S_max, float* workspace, int splits_max, void* ctx_bf16, void* stream);
+/* ---- FP8 (OCP e4m3) K / V cache, head_dim 128, bf16 q / ctx.  Per layer and stream two buffers of cap * KV * (128 + 4) bytes each (cap = S_max, a multiple of 64):
+ *   kcache : codes [S_max][KV*128] (rotated keys), then fp32 scales [S_max][KV] at byte offset S_max*KV*128
+ *   vtcache: codes [KV][128][S_max],               then fp32 scales [KV][S_max] at byte offset KV*128*S_max
+ * one scale per (token, KV head) row of 128 values = amax / 448 (1.0 for an all-zero row), code = RNE(x / scale) saturated at +-448; K is quantised after
+ * RoPE.  Buffers 16-byte aligned.
+ * sm_rope_kv_append with the fp8 caches as destination (q bf16 exactly as sm_rope_kv_append writes it) */
+int sm_rope_kv_append_fp8(const float* qkv, int n, int pos0, int H, int KV, int dh, const float* cos_tab, const float* sin_tab, void* q_bf16,
+                          void* kcache, void* vtcache, int S_max, void* stream);
+/* single-token decode attention over the fp8 cache, every context length: one launch up to 384 keys, else the keys are split over up to splits_max (<= 64)
+ * blocks per KV group and merged; window as sm_llm_decode_attention_window (0 = none); workspace fp32 [splits_max * H * (dh + 2)].  Positions past `pos` may
+ * hold any bytes. */
+int sm_llm_decode_attention_fp8(const void* q_bf16, const void* kcache, const void* vtcache, int pos, int H, int KV, int dh, int S_max, int window,
+                                float* workspace, int splits_max, void* ctx_bf16, void* stream);
+/* the same for S streams in one launch: DEVICE arrays of S K-buffer pointers, S V^T-buffer pointers and S positions (row t of q [S][H*dh] is stream t's query at
+ * pos_dev[t], ctx likewise); nk_max = the longest context incl. the new token (the caller's bookkeeping: it sizes the key splits, every stream takes the same
+ * number); the workspace fp32 [splits_max * H * (dh + 2)] serves ALL streams together (at most splits_max / S splits each, and never more than 64) */
+int sm_llm_decode_attention_fp8_tab(const void* q_bf16, const void* const* kc_tab_dev, const void* const* vtc_tab_dev, const int* pos_dev, int S, int nk_max, int H,
+                                    int KV, int dh, int S_max, int window, float* workspace, int splits_max, void* ctx_bf16, void* stream);
+/* codes * scale -> bf16 for keys [k_lo, k_hi): k_out bf16 [S_max][KV*dh], vt_out bf16 [KV*dh][S_max] (the 16-bit cache layout sm_llm_attention reads); nothing
+ * outside the range is written */
+int sm_kv_fp8_expand(const void* kcache, const void* vtcache, int k_lo, int k_hi, int KV, int dh, int S_max, void* k_out_bf16, void* vt_out_bf16, void* stream);
 /* out[m] = bf16( silu(gu[m][0:F]) * gu[m][F:2F] ) */
 int sm_swiglu(const float* gu, int M, int F, void* out_bf16, void* stream);
 /* greedy argmax over fp32 logits[V] -> token (int32, device) ; first max wins (torch.argmax)           */
@@ -383,6 +404,12 @@ int sm_model_set_weights_fp4(sm_model* m, int on);
  * of 129..512 rows run the tiled fp4 GEMM instead of expanding every image per call; everything up to 128 rows is unchanged.  Valid in the window of
  * sm_model_set_weights_fp4, after it; on = 0: off (the default).  SM_EINVAL unless on is 0 or 1, and for on = 1 without weights_fp4 = 2. */
 int sm_model_set_fp4_gemm(sm_model* m, int on);
+/* FP8 (e4m3) K / V cache for the LLM, one fp32 scale per (token, KV head): 2112 instead of 4096 bytes per token and layer at KV = 8, head_dim 128 (format: the
+ * operator section above).  on = 1: streams opened from now on hold fp8 caches; decode steps (sm_llm_decode, sm_group_llm_decode) read them directly, calls with
+ * more than one row (sm_llm_prefill, sm_llm_forward_logits) append fp8 and run the chunk attention on a per-call bf16 expansion of the keys they see.  on = 0:
+ * off (the default).  Call it before the first sm_stream_open.  SM_EINVAL for llm_fp16 models, a head_dim other than 128, on outside {0, 1}, and once a stream
+ * has been opened (it stays locked after the last stream closes). */
+int sm_model_set_kv_fp8(sm_model* m, int on);
 /* names of tensors still missing, '\n'-separated, into buf (for error messages) */
 int sm_model_missing(sm_model* m, char* buf, size_t buflen);
 
@@ -445,6 +472,8 @@ int sm_stream_set_kv_len(sm_stream* s, int n);            /* truncate the KV cac
  * buffers' addresses -- re-capture after sm_stream_kv_capacity changes (a captured step bakes the host-side position as well, so it was never valid
  * beyond the context it was captured at). */
 int sm_stream_kv_capacity(sm_stream* s);
+/* bytes the stream's K / V buffers hold right now, all layers (16-bit cache: layers * cap * 4 * KV * dh; fp8 cache: layers * cap * (2 * KV * dh + 8 * KV)); -1: bad handle */
+long sm_stream_kv_bytes(sm_stream* s);
 /* a10+a12 prefill: n new positions; ids[i] >= 0 text token, ids[i] < 0 -> frame token (-ids[i]-1).
  * Appends to the KV cache at kv_len, leaves the greedy next token in the stream (device).           */
 int sm_llm_prefill(sm_stream* s, const int32_t* ids_dev, int n, void* stream);

@@ -1382,3 +1382,249 @@ int sm_llm_decode_attention_seg(const void* q, const SmDecodeSeg& seg, int S, in
     SM_LAUNCH_CHECK();
     return SM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ decode over the FP8 (e4m3) K / V cache
+// One kernel for every context length: grid (stream, KV group, key split), NW waves per block, wave w of a block owns the 64-key blocks w, w + NW, ... of its split.
+// The cache format stands in common.h.  Per 64-key block a lane issues 8 + 8 sixteen-byte loads (K: 4 row fragments x 2 dim halves; V^T: 8 dim fragments) and two
+// dword loads (lane L: the K and the V scale of key key0 + L) -- half the loads of the 16-bit kernel for twice the keys; two blocks (128 keys) are in flight per
+// wave and round, everything issued before anything is consumed.
+//   S^T = K . Q^T : lane (i, g) reads the 16 codes of dims kk*64 + g*16 .. +15 (kk = 0, 1) of key key0 + (i>>2)*16 + a*4 + (i&3), a = 0..3.  The codes become bf16
+//                   in registers (v_cvt_scalef32_pk_bf16_fp8, exact: e4m3 is a subset of bf16) -- bytes 0..7 and 8..15 of a load are the A operands of two
+//                   k-steps, whose B operands are q at the SAME dims (the contraction order is free as long as both sides agree): q stays bf16, so the scores are
+//                   exact products of what the cache holds, accumulated in fp32, and the key's scale multiplies the fp32 score.  The row permutation makes lane
+//                   (q, g)'s accumulators a = 0..3, r = 0..3 the keys key0 + g*16 + a*4 + r: 16 consecutive keys.
+//   O^T = V^T . P^T: lane (i, g) reads the 16 codes of positions key0 + g*16 .. +15 of dim df*16 + i: bytes 0..7 / 8..15 are the A operands of two k-steps whose B
+//                   operands are the accumulators a = 0, 1 / a = 2, 3 register for register.  P is never fp8: P' = bf16(e * vscale[key]) carries the V scale (e4m3
+//                   has no normal below 2^-6; P * vscale sits far below that), the row sum adds the unscaled bf16-rounded e.
+// A lane's 16 scales sit in the 16 lanes of ITS row of the wave (lane g*16 + j holds key key0 + g*16 + j): sixteen in-row shuffles per scale vector.
+// Keys past the cache end or in front of the window may hold any bytes (NaN codes, NaN scales): their scores are SELECTED to -inf, their V scale to 0 and their V
+// codes to 0 before anything is multiplied.  The NW per-wave partial softmaxes meet in LDS; one split: the merged bf16 context; more: the merged partial in the
+// layout attn_combine_kernel reads (part_o [split][H][128], part_ml [split][H][2] = (max, sum)).
+struct DecFp8P {
+    const bf16_t* q; bf16_t* ctx;               // [S][H*128]
+    const uint8_t* k; const uint8_t* vt;        // single stream (nseg == 0)
+    SmDecodeSegTab tab;                         // nseg > 0: per-stream caches and positions, device-side
+    int nk, H, KV, S_max, nseg, window;
+    int bps, splits;                            // 64-key blocks per split; gridDim.z
+    float* part_o; float* part_ml; long part_bs;
+    float c;
+};
+__device__ __forceinline__ bf16x8 kv8_to_bf16(uint32_t lo, uint32_t hi) {
+    union { bf16x8 v; bf16x2 p[4]; } r;
+    r.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
+    r.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
+    r.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
+    r.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+    return r.v;
+}
+template <int NW>      // (two waves per SIMD either way: one 8-wave block or two 4-wave blocks per CU -- the second launch bound keeps the 4-wave form within 256 registers)
+__global__ __launch_bounds__(NW * 64, 8 / NW) void decode_attn_fp8_kernel(DecFp8P p) {
+    constexpr int DH = 128;
+    __shared__ float osh[NW][16][DH + 4];
+    __shared__ float msh[NW][16], lsh[NW][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x, kvh = blockIdx.y, z = blockIdx.z;
+    const int rep = p.H / p.KV;
+    const bool segm = p.nseg > 0;
+    int nk = segm ? p.tab.pos0[b] + p.tab.step + 1 : p.nk;
+    nk = min(max(nk, 1), p.S_max);
+    const uint8_t* kc = segm ? (const uint8_t*)p.tab.kc[b] : p.k;
+    const uint8_t* vt = segm ? (const uint8_t*)p.tab.vtc[b] : p.vt;
+    const size_t codes = (size_t)p.S_max * p.KV * DH;
+    const float* ksc = (const float*)(kc + codes) + kvh;                           // scale of key k: ksc[k * KV]
+    const float* vsc = (const float*)(vt + codes) + (size_t)kvh * p.S_max;         // vsc[k]
+    kc += kvh * DH;
+    vt += (size_t)kvh * DH * p.S_max;
+    const long k_rs = (long)p.KV * DH;
+    bf16x8 qf[4];                                  // k-step kk*2 + hf: dims kk*64 + g*16 + hf*8 .. +7
+    {
+        union { bf16x8 v; u32x4 u; } zr;
+        zr.u = u32x4{0, 0, 0, 0};
+        const bf16_t* src = p.q + ((size_t)b * p.H + kvh * rep + (i < rep ? i : 0)) * DH + g * 16;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qf[s] = i < rep ? *(const bf16x8*)(src + (s >> 1) * 64 + (s & 1) * 8) : zr.v;
+    }
+    f32x4 o[8];
+#pragma unroll
+    for (int df = 0; df < 8; ++df) o[df] = f32x4{0, 0, 0, 0};
+    float m_run = -INFINITY, l_run = 0.f;
+    const int k_lo = p.window > 0 ? max(0, nk - p.window) : 0;          // first visible key
+    const int blk_first = (k_lo >> 6) + z * p.bps;
+    const int blk_end = min((nk + 63) >> 6, blk_first + p.bps);
+    for (int blk0 = blk_first + wave; blk0 < blk_end; blk0 += 2 * NW) {
+        const bool two = blk0 + NW < blk_end;
+        u32x4 kq[2][4][2], vq[2][8];
+        float ksl[2], vsl[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (u == 1 && !two) break;
+            const int key0 = (blk0 + NW * u) * 64;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const uint8_t* src = kc + (long)(key0 + (i >> 2) * 16 + a * 4 + (i & 3)) * k_rs + g * 16;
+                kq[u][a][0] = *(const u32x4*)src;
+                kq[u][a][1] = *(const u32x4*)(src + 64);
+            }
+#pragma unroll
+            for (int df = 0; df < 8; ++df) vq[u][df] = *(const u32x4*)(vt + (size_t)(df * 16 + i) * p.S_max + key0 + g * 16);
+            ksl[u] = ksc[(size_t)(key0 + lane) * p.KV];
+            vsl[u] = vsc[key0 + lane];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (u == 1 && !two) break;
+            const int key0 = (blk0 + NW * u) * 64;
+            f32x4 sc[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                f32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    acc = mfma16<false>(kv8_to_bf16(kq[u][a][kk][0], kq[u][a][kk][1]), qf[kk * 2], acc);
+                    acc = mfma16<false>(kv8_to_bf16(kq[u][a][kk][2], kq[u][a][kk][3]), qf[kk * 2 + 1], acc);
+                }
+                sc[a] = acc;
+            }
+            float s[16], vs[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                s[j] = sc[j >> 2][j & 3] * __shfl(ksl[u], g * 16 + j, 64);
+                vs[j] = __shfl(vsl[u], g * 16 + j, 64);
+            }
+            const int kb = key0 + g * 16;                           // this lane's 16 keys: kb + j
+            if (key0 + 64 > nk || key0 < k_lo) {                    // only the last block of the cache and the first of a window carry dead keys
+                uint32_t keep[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const bool dead = kb + j >= nk || kb + j < k_lo;
+                    s[j] = dead ? -INFINITY : s[j];
+                    vs[j] = dead ? 0.f : vs[j];
+                    keep[j >> 2] |= dead ? 0u : (0xffu << (8 * (j & 3)));
+                }
+#pragma unroll
+                for (int df = 0; df < 8; ++df)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) vq[u][df][w] &= keep[w];
+            }
+            float mx = s[0];
+#pragma unroll
+            for (int j = 1; j < 16; ++j) mx = fmaxf(mx, s[j]);
+            mx = xor32_max(xor16_max(mx));
+            const float m_new = fmaxf(m_run, mx);            // finite: every block in [k_lo / 64, (nk - 1) / 64] holds a visible key
+            const float mc = (m_new == -INFINITY ? 0.f : m_new) * p.c;
+            const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run, p.c, -mc));
+            m_run = m_new;
+            float pe[16], psum = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float e = __builtin_amdgcn_exp2f(fmaf(s[j], p.c, -mc));
+                psum += bf2f(f2bf(e));                       // the row sum adds the rounded, unscaled e
+                pe[j] = e * vs[j];                           // the V scale rides in P, folded in before the one rounding to bf16
+            }
+            l_run = l_run * alpha + psum;
+            const float (&pe0)[8] = *(const float (*)[8])&pe[0];
+            const float (&pe1)[8] = *(const float (*)[8])&pe[8];
+            const bf16x8 pf0 = make8<false>(pe0), pf1 = make8<false>(pe1);
+#pragma unroll
+            for (int df = 0; df < 8; ++df) {
+                o[df] *= alpha;
+                o[df] = mfma16<false>(kv8_to_bf16(vq[u][df][0], vq[u][df][1]), pf0, o[df]);
+                o[df] = mfma16<false>(kv8_to_bf16(vq[u][df][2], vq[u][df][3]), pf1, o[df]);
+            }
+        }
+    }
+    // per-wave partial -> LDS (lane (i, g): query i, dims df*16 + g*4 + r; l still split over the four g's)
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (i < rep) {
+#pragma unroll
+        for (int df = 0; df < 8; ++df) *(f32x4*)&osh[wave][i][df * 16 + g * 4] = o[df];
+        if (g == 0) { msh[wave][i] = m_run; lsh[wave][i] = l_run; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < rep * DH; idx += NW * 64) {
+        const int qi = idx >> 7, d = idx & (DH - 1);
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, msh[w][qi]);
+        float num = 0.f, den = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = msh[w][qi];
+            const float wt = mw == -INFINITY ? 0.f : exp2f((mw - M) * p.c);
+            num += wt * osh[w][qi][d];
+            den += wt * lsh[w][qi];
+        }
+        const int head = kvh * rep + qi;
+        if (p.splits == 1) { p.ctx[((size_t)b * p.H + head) * DH + d] = (bf16_t)f2bf(num / den); continue; }
+        // a split that lies beyond a shorter stream's cache leaves (0, -inf, 0): weight 0 in the merge
+        const size_t row = (size_t)z * p.H + head;
+        p.part_o[b * p.part_bs + row * DH + d] = num;
+        if (d == 0) { float* ml = p.part_ml + b * p.part_bs + row * 2; ml[0] = M; ml[1] = den; }
+    }
+}
+// splits: the rule of the 16-bit path -- one up to 384 keys, or up to 2048 when the S x KV blocks fill the chip by themselves; beyond that the walked key range is
+// cut into enough splits for ~2 blocks per CU (at most `cap`, 64 -- attn_combine_kernel merges one split per lane -- and one per 64-key block)
+static void decode_fp8_plan(int nk_eff, int S, int KV, int cap, int* bps, int* splits) {
+    const int nblk = cdiv(nk_eff, 64);
+    int sp = 1;
+    if (!(nk_eff <= 384 || (S * KV >= 128 && nk_eff <= 2048))) {
+        sp = cdiv(512, S * KV);
+        if (sp > cap) sp = cap;
+        if (sp > 64) sp = 64;
+        if (sp > nblk) sp = nblk;
+        if (sp < 1) sp = 1;
+    }
+    *bps = cdiv(nblk, sp);
+    *splits = cdiv(nblk, *bps);
+}
+static int launch_decode_fp8(DecFp8P& d, int S, int nk_max, int dh, float* workspace, int ws_splits, hipStream_t st) {
+    // keys a stream walks: from the 64-key block of its first visible key to its newest (the rule of the 16-bit launchers)
+    const int nk_eff = d.window > 0 && nk_max > d.window + 63 ? d.window + 63 : nk_max;
+    decode_fp8_plan(nk_eff, S, d.KV, ws_splits / S, &d.bps, &d.splits);
+    SM_REQUIRE(d.splits == 1 || workspace, "decode attention (fp8 cache): %d keys need a workspace for the key splits", nk_max);
+    d.part_bs = (long)d.splits * d.H * (dh + 2);
+    d.part_o = workspace; d.part_ml = workspace ? workspace + (size_t)d.splits * d.H * dh : nullptr;
+    d.c = (1.0f / sqrtf((float)dh)) * 1.4426950408889634f;
+    {
+        SmProfScope prof(SM_PROF_ATTN, st);
+        const dim3 grid(S, d.KV, d.splits);
+        if (S > 1 && decode_attn_group_waves() == 4) decode_attn_fp8_kernel<4><<<grid, 256, 0, st>>>(d);
+        else decode_attn_fp8_kernel<8><<<grid, 512, 0, st>>>(d);
+        SM_LAUNCH_CHECK();
+    }
+    if (d.splits > 1) {
+        attn_combine_kernel<<<dim3(d.H, S), 64, 0, st>>>(d.part_o, d.part_ml, d.splits, d.H, dh, d.c, d.ctx, d.part_bs, d.part_bs, 0);
+        SM_LAUNCH_CHECK();
+    }
+    return SM_OK;
+}
+extern "C" int sm_llm_decode_attention_fp8(const void* q, const void* kcache, const void* vtcache, int pos, int H, int KV, int dh, int S_max, int window,
+                                           float* workspace, int splits_max, void* ctx, void* stream) {
+    SM_REQUIRE(q && kcache && vtcache && ctx && pos >= 0 && pos < S_max && window >= 0, "sm_llm_decode_attention_fp8: bad args");
+    SM_REQUIRE(dh == 128 && S_max % 64 == 0 && KV > 0 && H % KV == 0 && H / KV <= 16 && splits_max >= 1 && splits_max <= 64, "sm_llm_decode_attention_fp8: head_dim 128, S_max %% 64, H %% KV, H / KV <= 16, 1 <= splits_max <= 64");
+    SM_REQUIRE((((uintptr_t)q | (uintptr_t)kcache | (uintptr_t)vtcache) & 15) == 0, "sm_llm_decode_attention_fp8: q and the caches must be 16-byte aligned");
+    DecFp8P d;
+    d.q = (const bf16_t*)q; d.ctx = (bf16_t*)ctx; d.k = (const uint8_t*)kcache; d.vt = (const uint8_t*)vtcache;
+    d.tab = SmDecodeSegTab{nullptr, nullptr, nullptr, 0};
+    d.nk = pos + 1; d.H = H; d.KV = KV; d.S_max = S_max; d.nseg = 0; d.window = window;
+    return launch_decode_fp8(d, 1, pos + 1, dh, workspace, splits_max, (hipStream_t)stream);
+}
+// S streams in one launch (+ the merge launch when the keys are split): the table form.  workspace: fp32 [splits_max * H * (dh + 2)] for ALL streams together
+// (every stream takes the same number of splits, sized for the longest context: at most splits_max / S)
+int sm_llm_decode_attention_fp8_seg_tab(const void* q, const SmDecodeSegTab& tab, int S, int nk_max, int H, int KV, int dh, int S_max, int window, float* workspace,
+                                        int splits_max, void* ctx, void* stream) {
+    SM_REQUIRE(q && ctx && S > 0 && tab.kc && tab.vtc && tab.pos0 && nk_max >= 1 && nk_max <= S_max && window >= 0, "sm_llm_decode_attention_fp8_tab: bad args");
+    SM_REQUIRE(dh == 128 && S_max % 64 == 0 && KV > 0 && H % KV == 0 && H / KV <= 16 && splits_max >= 1, "sm_llm_decode_attention_fp8_tab: head_dim 128, S_max %% 64, H %% KV, H / KV <= 16");
+    DecFp8P d;
+    d.q = (const bf16_t*)q; d.ctx = (bf16_t*)ctx; d.k = nullptr; d.vt = nullptr;
+    d.tab = tab;
+    d.nk = nk_max; d.H = H; d.KV = KV; d.S_max = S_max; d.nseg = S; d.window = window;
+    return launch_decode_fp8(d, S, nk_max, dh, workspace, splits_max, (hipStream_t)stream);
+}
+extern "C" int sm_llm_decode_attention_fp8_tab(const void* q, const void* const* kc_tab_dev, const void* const* vtc_tab_dev, const int* pos_dev, int S, int nk_max, int H,
+                                               int KV, int dh, int S_max, int window, float* workspace, int splits_max, void* ctx, void* stream) {
+    const SmDecodeSegTab tab = {(void* const*)kc_tab_dev, (void* const*)vtc_tab_dev, pos_dev, 0};
+    return sm_llm_decode_attention_fp8_seg_tab(q, tab, S, nk_max, H, KV, dh, S_max, window, workspace, splits_max, ctx, stream);
+}

@@ -171,3 +171,14 @@ __host__ __device__ __forceinline__ size_t packed_index(int n, int k, int KS) {
 //     scales  [q 0..ceil(KS/4))[lane 0..63][4 B] byte h of lane (g, i)'s dword = the e8m0 byte of ITS block of code chunk 4q + h
 //                                               (the lane that feeds scale_a holds its own scale; padding bytes are 127)
 __host__ __device__ __forceinline__ size_t fp4_rg_bytes(int KS) { return (size_t)KS * 1024 + (size_t)((KS + 3) >> 2) * 256; }
+
+// FP8 K / V cache (sm_model_set_kv_fp8; head_dim 128, bf16-operand models): per layer and stream the same TWO buffers as the 16-bit cache, `cap` = the cache
+// pitch the kernels receive as S_max (tokens, a multiple of 64):
+//   K buffer    codes  [cap][KV * 128]      one OCP e4m3 byte per element, rotated (post-RoPE) keys
+//               scales [cap][KV] fp32       at byte offset cap * KV * 128 of the same allocation
+//   V^T buffer  codes  [KV][128][cap]       d-major, positions contiguous
+//               scales [KV][cap] fp32       at byte offset KV * 128 * cap
+//   one scale per (token, KV head) row of 128 values: amax / 448, 1.0 when amax == 0; code = RNE(x / scale) saturated at +-448 (the NaN codes 0x7F / 0xFF are never
+//   written).  2112 bytes per token and layer at KV = 8 instead of 4096.  Producers: kv_fp8.hip; consumers: decode_attn_fp8_kernel (attention.hip, reads the codes in
+//   MFMA operand order) and kv_fp8_expand_kernel (kv_fp8.hip: codes * scale -> bf16 for the chunk attention kernels).
+__host__ __device__ __forceinline__ size_t kv_fp8_buf_bytes(int cap, int KV) { return (size_t)cap * KV * 128 + (size_t)cap * KV * 4; }

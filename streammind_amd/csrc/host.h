@@ -86,6 +86,12 @@ int sm_llm_decode_attention_seg_tab(const void* q_bf16, const SmDecodeSegTab& ta
                                     void* stream, int window);                                                       // attention.hip
 int sm_rope_kv_append_seg_tab(const float* qkv, int S, int H, int KV, int dh, const float* cos_tab, const float* sin_tab, void* q_bf16,
                               const SmDecodeSegTab& tab, int S_max, int f16, void* stream, int nslab = 0, size_t slab_stride = 0);   // vecops.hip (nslab > 0: qkv = unsummed split-K slabs)
+// the FP8 K / V cache (common.h) in the batched decode step: one RoPE + quantise + append launch and one attention launch (+ the split merge) for any number of
+// streams through the device-side table; workspace of the attention: fp32 [splits_max * H * (dh + 2)] for all streams together
+int sm_rope_kv_append_fp8_seg_tab(const float* qkv, int S, int H, int KV, int dh, const float* cos_tab, const float* sin_tab, void* q_bf16,
+                                  const SmDecodeSegTab& tab, int S_max, void* stream, int nslab = 0, size_t slab_stride = 0);       // kv_fp8.hip
+int sm_llm_decode_attention_fp8_seg_tab(const void* q_bf16, const SmDecodeSegTab& tab, int S, int nk_max, int H, int KV, int dh, int S_max, int window,
+                                        float* workspace, int splits_max, void* ctx_bf16, void* stream);                            // attention.hip
 int sm_llm_attention_ex(const void* q, const void* kcache, const void* vtcache, int n, int pos0, int H, int KV, int dh, int S_max,
                         void* ctx, int f16, void* stream, int window = 0);
 int sm_llm_decode_attention_ex(const void* q, const void* kcache, const void* vtcache, int pos, int H, int KV, int dh, int S_max,

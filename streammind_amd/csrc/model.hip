@@ -136,6 +136,9 @@ struct sm_model {
     int weights_fp4 = 0;           // sm_model_set_weights_fp4's mode: 0 off, 1 SM_W_FP4, 2 SM_W_FP4_MFMA (not part of sm_config_t: the struct is ABI)
     bool fp4_gemm = false;         // sm_model_set_fp4_gemm: mode 2's slots go out as SM_W_FP4_GEMM (the tiled fp4 GEMM above 128 rows)
     bool any_loaded = false;       // a tensor has been handed over: the weight formats are fixed from here on
+    bool kv_fp8 = false;           // sm_model_set_kv_fp8: streams hold e4m3 K / V caches with one fp32 scale per (token, KV head) (format: common.h)
+    int streams_opened = 0;        // the cache format is fixed once a stream has been opened (never counted down: a stream may outlive its model's handle in a
+                                   // host binding, so closing one does not touch the model; the switch stays locked after the last stream closes)
     std::unordered_map<std::string, Slot> slots;           // canonical name -> storage
     struct Route { std::string slot; int row0; int rows; int part; };   // checkpoint name -> (slot, first row, row count, index of this part)
     std::unordered_map<std::string, Route> routes;
@@ -173,7 +176,8 @@ struct sm_model {
     // Mistral-7B widths, i.e. 97 GB of idle scratch beside 512 open streams).  A call's rows live here only for the duration of the call -- what a stream
     // carries from call to call (pending token, last logits, K / V, frame tokens, Mamba state) stays in the stream -- so streams driven on one HIP stream
     // share a set in stream order, and a reply on the LLM lane (its own HIP stream) has its own.
-    struct LlmWs { DevBuf emb, xnb, qkvf, qb, ctxb, actb, attn_ws; };
+    struct LlmWs { DevBuf emb, xnb, qkvf, qb, ctxb, actb, attn_ws;
+                   DevBuf kexp, vtexp; };     // fp8 K / V cache: the bf16 expansion a chunk call's attention reads (K [cap][kn], V^T [kn][cap]; kv_fp8_scratch)
     static constexpr int LLM_CHUNK = 2048;          // rows of a prefill / teacher-forced chunk
     std::map<void*, std::unique_ptr<LlmWs>> llm_ws;
     int llm_workspace(void* stream, LlmWs** out) {
@@ -614,6 +618,15 @@ extern "C" int sm_model_set_weights_fp4(sm_model* m, int on) {
         if (kv.second.kind == 1 && kv.first.rfind("llm.model.layers.", 0) == 0) kv.second.fp4 = on != 0;
     return SM_OK;
 }
+extern "C" int sm_model_set_kv_fp8(sm_model* m, int on) {
+    SM_REQUIRE(m, "sm_model_set_kv_fp8: null model");
+    SM_REQUIRE(on == 0 || on == 1, "sm_model_set_kv_fp8: on = %d (0 off, 1 the fp8 K / V cache)", on);
+    SM_REQUIRE(m->streams_opened == 0, "sm_model_set_kv_fp8: call it before the first sm_stream_open (the cache format of a model's streams is fixed once one exists)");
+    SM_REQUIRE(!on || !m->c.llm_fp16, "sm_model_set_kv_fp8: exclusive with llm_fp16 (the fp8 cache feeds bf16 operands)");
+    SM_REQUIRE(!on || (m->c.llm_layers > 0 && m->c.llm_heads > 0 && m->c.llm_hidden / m->c.llm_heads == 128), "sm_model_set_kv_fp8: the fp8 K / V cache takes head_dim 128 only");
+    m->kv_fp8 = on != 0;
+    return SM_OK;
+}
 // mode 2 only: prefill chunks above 128 rows on the tiled fp4 GEMM (SM_W_FP4_GEMM) instead of the per-call expansion.  Same window as the setter above.
 extern "C" int sm_model_set_fp4_gemm(sm_model* m, int on) {
     SM_REQUIRE(m && !m->any_loaded && !m->finalized, "sm_model_set_fp4_gemm: call it between sm_model_create and the first sm_model_load_tensor");
@@ -996,18 +1009,28 @@ static int kv_set_cap(sm_stream* s, int new_cap, void* stream) {
         if (hipStreamIsCapturing(st, &cs) == hipSuccess) SM_REQUIRE(cs == hipStreamCaptureStatusNone, "kv_reserve: the K / V cache must grow (%d -> %d tokens) but the HIP stream is capturing: run the step eagerly once at this context first", s->cap, new_cap);
         else (void)hipGetLastError(); }
     const int dh = c.llm_hidden / c.llm_heads, kn = c.llm_kv_heads * dh;
+    const bool fp8 = s->m->kv_fp8;
+    const size_t buf_bytes = fp8 ? kv_fp8_buf_bytes(new_cap, c.llm_kv_heads) : (size_t)new_cap * kn * 2;
     std::vector<DevBuf> nk(c.llm_layers), nv(c.llm_layers);
     int rc = 0;
     for (int l = 0; l < c.llm_layers && !rc; ++l) {
-        rc = nk[l].alloc((size_t)new_cap * kn * 2, false);
-        if (!rc) rc = nv[l].alloc((size_t)kn * new_cap * 2, false);
+        rc = nk[l].alloc(buf_bytes, false);
+        if (!rc) rc = nv[l].alloc(buf_bytes, false);
     }
     if (rc) return rc;
     const int live = s->kv_len;
     for (int l = 0; l < c.llm_layers; ++l) {
-        SM_HIP(hipMemsetAsync(nk[l].p, 0, (size_t)new_cap * kn * 2, st));
-        SM_HIP(hipMemsetAsync(nv[l].p, 0, (size_t)kn * new_cap * 2, st));
-        if (live > 0) {
+        SM_HIP(hipMemsetAsync(nk[l].p, 0, buf_bytes, st));
+        SM_HIP(hipMemsetAsync(nv[l].p, 0, buf_bytes, st));
+        if (live > 0 && fp8) {
+            // codes and scales separately: the scales start behind the codes, so their offset moves with the capacity
+            const int KV = c.llm_kv_heads;
+            const char* ok = (const char*)s->kc[l].p; const char* ov = (const char*)s->vtc[l].p;
+            SM_HIP(hipMemcpyAsync(nk[l].p, ok, (size_t)live * kn, hipMemcpyDeviceToDevice, st));
+            SM_HIP(hipMemcpyAsync((char*)nk[l].p + (size_t)new_cap * kn, ok + (size_t)s->cap * kn, (size_t)live * KV * 4, hipMemcpyDeviceToDevice, st));
+            SM_HIP(hipMemcpy2DAsync(nv[l].p, (size_t)new_cap, ov, (size_t)s->cap, (size_t)live, kn, hipMemcpyDeviceToDevice, st));
+            SM_HIP(hipMemcpy2DAsync((char*)nv[l].p + (size_t)new_cap * kn, (size_t)new_cap * 4, ov + (size_t)s->cap * kn, (size_t)s->cap * 4, (size_t)live * 4, KV, hipMemcpyDeviceToDevice, st));
+        } else if (live > 0) {
             SM_HIP(hipMemcpyAsync(nk[l].p, s->kc[l].p, (size_t)live * kn * 2, hipMemcpyDeviceToDevice, st));
             SM_HIP(hipMemcpy2DAsync(nv[l].p, (size_t)new_cap * 2, s->vtc[l].p, (size_t)s->cap * 2, (size_t)live * 2, kn, hipMemcpyDeviceToDevice, st));
         }
@@ -1027,6 +1050,13 @@ static int kv_reserve(sm_stream* s, int need, void* stream) {
     return kv_set_cap(s, nc, stream);
 }
 extern "C" int sm_stream_kv_capacity(sm_stream* s) { return s ? s->cap : -1; }
+extern "C" long sm_stream_kv_bytes(sm_stream* s) {
+    if (!s) return -1;
+    size_t b = 0;
+    for (const DevBuf& d : s->kc) b += d.bytes;
+    for (const DevBuf& d : s->vtc) b += d.bytes;
+    return (long)b;
+}
 
 extern "C" int sm_stream_open(sm_model* m, int max_frames, int max_seq, sm_stream** out) {
     SM_REQUIRE(m && m->finalized && out && max_frames > 0, "sm_stream_open: bad args / model not finalized");
@@ -1046,9 +1076,10 @@ extern "C" int sm_stream_open(sm_model* m, int max_frames, int max_seq, sm_strea
         const int ld = c.llm_hidden, dh = ld / c.llm_heads, kn = c.llm_kv_heads * dh, qn = c.llm_heads * dh;
         s->kc.resize(c.llm_layers); s->vtc.resize(c.llm_layers);
         s->cap = kv_initial_cap(max_seq);
+        const size_t buf_bytes = m->kv_fp8 ? kv_fp8_buf_bytes(s->cap, c.llm_kv_heads) : (size_t)s->cap * kn * 2;
         for (int l = 0; l < c.llm_layers && !rc; ++l) {
-            rc = s->kc[l].alloc((size_t)s->cap * kn * 2, true);
-            if (!rc) rc = s->vtc[l].alloc((size_t)kn * s->cap * 2, true);
+            rc = s->kc[l].alloc(buf_bytes, true);
+            if (!rc) rc = s->vtc[l].alloc(buf_bytes, true);
         }
         (void)qn;
         A(lmlog, (size_t)c.llm_vocab * 4, false); A(next_tok, 64, true);
@@ -1075,6 +1106,7 @@ extern "C" int sm_stream_open(sm_model* m, int max_frames, int max_seq, sm_strea
     }
 #undef A
     if (rc) { delete s; return rc; }
+    m->streams_opened++;
     *out = s;
     return SM_OK;
 }
@@ -1432,7 +1464,8 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
         if (!fuse_norm && l == 0 && (rc = sm_norm_ex(x, n, ld, ld, w.ln1_w, nullptr, c.llm_eps, 0, nullptr, W->xnb.p, ld, od, stream))) return rc;
         // decode: RoPE + KV append ride in the epilogue of the q/k/v product (no fp32 q/k/v round trip, one launch less per layer)
         // (fp4 weights: the plain q|k|v product and the RoPE / append launch)
-        const bool fuse_rope = fuse_norm && dh == 128 && ld >= 1024 && !g_no_fused_rope && !w.qkv->fp4;
+        // (fp8 K / V cache: likewise -- the append quantises whole rows, it is the fp8 launch below)
+        const bool fuse_rope = fuse_norm && dh == 128 && ld >= 1024 && !g_no_fused_rope && !w.qkv->fp4 && !m->kv_fp8;
         {   sm_linear_t a = fuse_norm ? lin(m, *w.qkv, x, SM_X_F32, n, ld) : lin(m, *w.qkv, W->xnb.p, SM_X_BF16, n, ld);
             if (fuse_norm) { a.norm_gamma = w.ln1_w; a.norm_eps = c.llm_eps; }
             if (fuse_rope) {
@@ -1446,10 +1479,24 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
                 if ((rc = sm_linear(&a, stream))) return rc;
             }
         }
-        if (!fuse_rope && (rc = sm_rope_kv_append_ex(W->qkvf.as<float>(), n, s->kv_len, H, KV, dh, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p, s->kc[l].p, s->vtc[l].p, s->cap, f16, stream))) return rc;
-        if (n == 1) {
-            if ((rc = sm_llm_decode_attention_ex(W->qb.p, s->kc[l].p, s->vtc[l].p, s->kv_len, H, KV, dh, s->cap, W->attn_ws.as<float>(), SM_DECODE_SPLITS, W->ctxb.p, f16, stream, c.llm_sliding_window))) return rc;
-        } else if ((rc = sm_llm_attention_ex(W->qb.p, s->kc[l].p, s->vtc[l].p, n, s->kv_len, H, KV, dh, s->cap, W->ctxb.p, f16, stream, c.llm_sliding_window))) return rc;
+        if (m->kv_fp8) {
+            // fp8 cache: append as fp8; one row reads the codes directly, a chunk expands the keys it sees ([first visible key's tile, kv_len + n)) into the bf16
+            // scratch of this HIP stream and runs the chunk attention on that -- chunk and decode attention see the same dequantised values
+            if ((rc = sm_rope_kv_append_fp8(W->qkvf.as<float>(), n, s->kv_len, H, KV, dh, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p, s->kc[l].p, s->vtc[l].p, s->cap, stream))) return rc;
+            if (n == 1) {
+                if ((rc = sm_llm_decode_attention_fp8(W->qb.p, s->kc[l].p, s->vtc[l].p, s->kv_len, H, KV, dh, s->cap, c.llm_sliding_window, W->attn_ws.as<float>(), SM_DECODE_SPLITS, W->ctxb.p, stream))) return rc;
+            } else {
+                SM_REQUIRE(W->kexp.bytes >= (size_t)s->cap * kn * 2, "llm_layers: the fp8 cache's expansion scratch is smaller than the stream's capacity %d", s->cap);
+                const int k_lo = c.llm_sliding_window > 0 ? (s->kv_len - c.llm_sliding_window + 1 > 0 ? (s->kv_len - c.llm_sliding_window + 1) & ~63 : 0) : 0;
+                if ((rc = sm_kv_fp8_expand(s->kc[l].p, s->vtc[l].p, k_lo, s->kv_len + n, KV, dh, s->cap, W->kexp.p, W->vtexp.p, stream))) return rc;
+                if ((rc = sm_llm_attention_ex(W->qb.p, W->kexp.p, W->vtexp.p, n, s->kv_len, H, KV, dh, s->cap, W->ctxb.p, 0, stream, c.llm_sliding_window))) return rc;
+            }
+        } else {
+            if (!fuse_rope && (rc = sm_rope_kv_append_ex(W->qkvf.as<float>(), n, s->kv_len, H, KV, dh, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p, s->kc[l].p, s->vtc[l].p, s->cap, f16, stream))) return rc;
+            if (n == 1) {
+                if ((rc = sm_llm_decode_attention_ex(W->qb.p, s->kc[l].p, s->vtc[l].p, s->kv_len, H, KV, dh, s->cap, W->attn_ws.as<float>(), SM_DECODE_SPLITS, W->ctxb.p, f16, stream, c.llm_sliding_window))) return rc;
+            } else if ((rc = sm_llm_attention_ex(W->qb.p, s->kc[l].p, s->vtc[l].p, n, s->kv_len, H, KV, dh, s->cap, W->ctxb.p, f16, stream, c.llm_sliding_window))) return rc;
+        }
         {   sm_linear_t a = lin(m, *w.o, W->ctxb.p, SM_X_BF16, n, qn);
             a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
             if (!fuse_norm) { a.post_ln_gamma = w.ln2_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = W->xnb.p; a.post_ln_ldo = ld; }
@@ -1508,6 +1555,24 @@ static int llm_head(sm_stream* s, sm_model::LlmWs* W, int row, void* stream, int
     return SM_OK;
 }
 
+// fp8 K / V cache: the bf16 expansion scratch of this HIP stream's workspace set, sized to the stream's capacity.  Grown (zeroed: the chunk attention multiplies
+// P = 0 with whatever lies between the last key and the end of its 64-key tile) only here, behind kv_reserve -- where the cache itself may allocate; never
+// inside a captured step (decode steps do not touch it).
+static int kv_fp8_scratch(sm_stream* s, sm_model::LlmWs* W, void* stream) {
+    if (!s->m->kv_fp8) return SM_OK;
+    const sm_config_t& c = s->m->c;
+    const size_t need = (size_t)s->cap * c.llm_kv_heads * (c.llm_hidden / c.llm_heads) * 2;
+    if (W->kexp.bytes >= need) return SM_OK;
+    hipStream_t st = (hipStream_t)stream;
+    {   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess) SM_REQUIRE(cs == hipStreamCaptureStatusNone, "kv_fp8_scratch: the expansion scratch must grow to %d tokens but the HIP stream is capturing", s->cap);
+        else (void)hipGetLastError(); }
+    SM_HIP(hipStreamSynchronize(st));            // the old scratch may still be read by kernels enqueued before this call
+    int rc;
+    if ((rc = W->kexp.alloc(need, true)) || (rc = W->vtexp.alloc(need, true))) return rc;
+    return SM_OK;
+}
+
 extern "C" int sm_llm_prefill(sm_stream* s, const int32_t* ids, int n, void* stream) {
     SM_REQUIRE(s && ids && n > 0 && s->m->c.llm_layers > 0, "sm_llm_prefill: bad args / perception-only model");
     SM_REQUIRE(s->kv_len + n <= s->max_seq, "sm_llm_prefill: context %d + %d exceeds max_seq %d", s->kv_len, n, s->max_seq);
@@ -1516,7 +1581,7 @@ extern "C" int sm_llm_prefill(sm_stream* s, const int32_t* ids, int n, void* str
     const int ld = m->c.llm_hidden;
     int rc, done = 0, last_rows = 0;
     sm_model::LlmWs* W;
-    if ((rc = m->llm_workspace(stream, &W)) || (rc = kv_reserve(s, s->kv_len + n, stream))) return rc;
+    if ((rc = m->llm_workspace(stream, &W)) || (rc = kv_reserve(s, s->kv_len + n, stream)) || (rc = kv_fp8_scratch(s, W, stream))) return rc;
     while (done < n) {
         int cur = n - done < sm_model::LLM_CHUNK ? n - done : sm_model::LLM_CHUNK;
         if ((rc = sm_embed_splice_ex(ids + done, cur, m->R.embed->buf.p, s->tokens.as<float>(), ld, W->emb.as<float>(), m->c.llm_fp16 ? 1 : 0, m->c.llm_vocab, s->max_frames, stream))) return rc;
@@ -1535,7 +1600,7 @@ extern "C" int sm_llm_forward_logits(sm_stream* s, const int32_t* ids, int n, fl
     const int ld = c.llm_hidden, V = c.llm_vocab;
     int rc, done = 0;
     sm_model::LlmWs* W;
-    if ((rc = m->llm_workspace(stream, &W)) || (rc = kv_reserve(s, s->kv_len + n, stream))) return rc;
+    if ((rc = m->llm_workspace(stream, &W)) || (rc = kv_reserve(s, s->kv_len + n, stream)) || (rc = kv_fp8_scratch(s, W, stream))) return rc;
     while (done < n) {
         const int cur = n - done < sm_model::LLM_CHUNK ? n - done : sm_model::LLM_CHUNK;
         if ((rc = sm_embed_splice_ex(ids + done, cur, m->R.embed->buf.p, s->tokens.as<float>(), ld, W->emb.as<float>(), m->c.llm_fp16 ? 1 : 0, m->c.llm_vocab, s->max_frames, stream))) return rc;
@@ -1642,7 +1707,9 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
     // streams x 32 layers), so that RoPE + append and the attention of ALL streams are one launch each per layer -- they were one launch per 128 streams
     // (pointer packs by value: 4 + 4 launches per layer at 512 streams).  SM_DECODE_TAB=0: the packs (A/B)
     static const bool tab_env = [] { const char* e = getenv("SM_DECODE_TAB"); return !e || atoi(e) != 0; }();
-    const bool use_tab = tab_env && NC > 1;
+    // fp8 K / V cache: the table for every S > 1 -- its append and attention kernels exist in the table form only, one launch each per layer
+    const bool fp8 = m->kv_fp8;
+    const bool use_tab = fp8 || (tab_env && NC > 1);
     void* const* tab_kc = nullptr; void* const* tab_vtc = nullptr; const int* tab_pos0 = nullptr;
     int kv_max0 = 0;
     if (use_tab) {
@@ -1703,7 +1770,7 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
         // up to 8 active streams: RoPE + KV append ride in the epilogue of the q/k/v product, every row against ITS stream's cache and position (the per-row
         // form of the kernel a stream's own decode step uses: one launch and the fp32 q/k/v round trip less per layer); its activations are fp32 rows, so the
         // norm in front of it leaves fp32.  Worth 0.4-1 % on bf16 weights and 2-3 % on fp8 weights at 2..8 streams (same box), nothing at 12.
-        const bool fuse_rope = S <= 8 && dh == 128 && ld >= 1024 && (ld & 31) == 0 && !g_no_fused_rope && !m->weights_fp4;
+        const bool fuse_rope = S <= 8 && dh == 128 && ld >= 1024 && (ld & 31) == 0 && !g_no_fused_rope && !m->weights_fp4 && !fp8;
         if (!fuse_norm && c.llm_layers > 0 &&
             (rc = sm_norm_ex(x, S, ld, ld, m->R.llm[0].ln1_w, nullptr, c.llm_eps, 0, fuse_rope ? g->d_xn32.as<float>() : nullptr, fuse_rope ? nullptr : g->d_xnb.p, ld, od, stream))) return rc;
         for (int l = 0; l < c.llm_layers; ++l) {
@@ -1722,11 +1789,18 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
                 } else {
                     a.out_f32 = g->d_qkvf.as<float>(); a.ldo = qn + 2 * kn;
                     // with the table path the RoPE kernel can sum the product's split-K slabs itself (33..128 streams: five slabs; one launch less per layer)
-                    if (use_tab) { if ((rc = sm_linear_leave_slabs(&a, &qkv_slabs, stream))) return rc; }
+                    if (use_tab && NC > 1) { if ((rc = sm_linear_leave_slabs(&a, &qkv_slabs, stream))) return rc; }
                     else if ((rc = sm_linear(&a, stream))) return rc;
                 }
             }
-            if (NC > 1 && use_tab) {           // every stream in ONE RoPE + append launch and ONE attention launch (device-side pointer table)
+            if (use_tab && fp8) {              // fp8 cache: quantise + append, then the fp8 decode kernel (key splits sized so that the partials of all streams fit d_ws)
+                SmDecodeSegTab tab = {tab_kc + (size_t)l * S, tab_vtc + (size_t)l * S, tab_pos0, j};
+                const float* qsrc = qkv_slabs.S > 0 ? qkv_slabs.ws : g->d_qkvf.as<float>();
+                if ((rc = sm_rope_kv_append_fp8_seg_tab(qsrc, S, H, KV, dh, m->rope_cos.as<float>(), m->rope_sin.as<float>(), g->d_qb.p, tab, S_max, stream, qkv_slabs.S, qkv_slabs.stride))) return rc;
+                if ((rc = sm_llm_decode_attention_fp8_seg_tab(g->d_qb.p, tab, S, kv_max0 + j + 1, H, KV, dh, S_max, c.llm_sliding_window, g->d_ws.as<float>(), SM_MAX_SEG * SM_DECODE_SPLITS,
+                                                              g->d_ctxb.p, stream))) return rc;
+                rope_done = attn_done = true;
+            } else if (use_tab) {              // every stream in ONE RoPE + append launch and ONE attention launch (device-side pointer table)
                 SmDecodeSegTab tab = {tab_kc + (size_t)l * S, tab_vtc + (size_t)l * S, tab_pos0, j};
                 const float* qsrc = qkv_slabs.S > 0 ? qkv_slabs.ws : g->d_qkvf.as<float>();
                 if ((rc = sm_rope_kv_append_seg_tab(qsrc, S, H, KV, dh, m->rope_cos.as<float>(), m->rope_sin.as<float>(), g->d_qb.p, tab, S_max, f16, stream, qkv_slabs.S, qkv_slabs.stride))) return rc;

@@ -63,6 +63,7 @@ class PathConfig:
     weights_fp4: int = 0           # opt-in: the LLM's q|k|v, o, gate|up, down as MXFP4 images (sm_model_set_weights_fp4; exclusive with weights_fp8 / llm_fp16).
                                    # the setter's mode: True / 1 = expansion above 16 rows, 2 = the fp4 weight stream up to 128 rows (group decode up to 128 streams)
     fp4_gemm: bool = False         # opt-in, needs weights_fp4 = 2: prefill chunks above 128 rows on the tiled fp4 GEMM instead of the per-call expansion (sm_model_set_fp4_gemm)
+    kv_fp8: bool = False           # opt-in: the LLM's K / V cache as e4m3 codes + one fp32 scale per (token, KV head) (sm_model_set_kv_fp8; head_dim 128, exclusive with llm_fp16)
     vit_fp16: bool = False         # vision-tower operands in IEEE fp16 (the reference demo's precision) instead of bf16
     llm_fp16: bool = False         # the same for the LLM (weights, embedding table, activations, q / KV caches, attention P)
     proj_fp16: bool = False        # the same for the connector + gate weights (activations as fp16 hi/lo pairs in precise mode)
@@ -123,6 +124,8 @@ class NativeModel:
             check(self.lib.sm_model_set_weights_fp4(self.h, int(cfg.weights_fp4)), "sm_model_set_weights_fp4")
         if getattr(cfg, "fp4_gemm", False):
             check(self.lib.sm_model_set_fp4_gemm(self.h, 1), "sm_model_set_fp4_gemm")
+        if getattr(cfg, "kv_fp8", False):            # the cache format of the model's streams: before the first open_stream
+            check(self.lib.sm_model_set_kv_fp8(self.h, 1), "sm_model_set_kv_fp8")
         self.finalized = False
         self.ignored = []
 
@@ -221,6 +224,10 @@ class NativeStream:
     def kv_capacity(self) -> int:
         """tokens the K / V cache holds room for right now (grows with the context up to max_seq: sm_stream_kv_capacity)"""
         return self.lib.sm_stream_kv_capacity(self.h)
+
+    def kv_bytes(self) -> int:
+        """bytes the K / V buffers of all layers hold right now (sm_stream_kv_bytes): 4 KV dh per token and layer, 2 KV dh + 8 KV with kv_fp8"""
+        return int(self.lib.sm_stream_kv_bytes(self.h))
 
     def push_pooled(self, pooled: torch.Tensor):
         assert pooled.dtype == torch.float32 and pooled.is_cuda and pooled.is_contiguous()
