@@ -309,6 +309,16 @@ int sm_llm_decode_attention_fp8_tab(const void* q_bf16, const void* const* kc_ta
 /* codes * scale -> bf16 for keys [k_lo, k_hi): k_out bf16 [S_max][KV*dh], vt_out bf16 [KV*dh][S_max] (the 16-bit cache layout sm_llm_attention reads); nothing
  * outside the range is written */
 int sm_kv_fp8_expand(const void* kcache, const void* vtcache, int k_lo, int k_hi, int KV, int dh, int S_max, void* k_out_bf16, void* vt_out_bf16, void* stream);
+/* causal attention of n >= 1 new rows (positions pos0 .. pos0 + n - 1, already appended) straight over the fp8 cache -- no expansion: q bf16 [n][H*dh], ctx bf16
+ * [n][H*dh], H / KV in {1, 2, 4, 8}, window as sm_llm_attention_window (0 = none).  The arithmetic is sm_llm_decode_attention_fp8's (codes -> bf16 exactly, bf16
+ * MFMA, K scale on the fp32 score, V scale inside the bf16 P).  A 128-row tile is 128 / (H / KV) consecutive queries x the heads of one K / V group; when the
+ * tiles x groups leave compute units idle the visible keys are split over blocks and merged.  workspace: fp32, splits * n * H * (dh + 2) floats are used; the
+ * most generous rule takes splits = min(64, compute units / (query tiles * KV), visible 64-key tiles / 4), i.e. never more than 64 * n * H * (dh + 2) floats;
+ * a smaller workspace_floats caps the splits at workspace_floats / (n * H * (dh + 2)); workspace NULL: one split whatever the shape.
+ * Positions >= pos0 + n, and with a window positions < pos0 - window + 1, may hold any bytes.  SM_EINVAL: dh != 128, H % KV != 0, H / KV not in {1, 2, 4, 8},
+ * S_max % 64 != 0, pos0 + n > S_max. */
+int sm_llm_attention_fp8(const void* q_bf16, const void* kcache, const void* vtcache, int n, int pos0, int H, int KV, int dh, int S_max, int window,
+                         float* workspace, size_t workspace_floats, void* ctx_bf16, void* stream);
 /* out[m] = bf16( silu(gu[m][0:F]) * gu[m][F:2F] ) */
 int sm_swiglu(const float* gu, int M, int F, void* out_bf16, void* stream);
 /* greedy argmax over fp32 logits[V] -> token (int32, device) ; first max wins (torch.argmax)           */
@@ -406,10 +416,17 @@ int sm_model_set_weights_fp4(sm_model* m, int on);
 int sm_model_set_fp4_gemm(sm_model* m, int on);
 /* FP8 (e4m3) K / V cache for the LLM, one fp32 scale per (token, KV head): 2112 instead of 4096 bytes per token and layer at KV = 8, head_dim 128 (format: the
  * operator section above).  on = 1: streams opened from now on hold fp8 caches; decode steps (sm_llm_decode, sm_group_llm_decode) read them directly, calls with
- * more than one row (sm_llm_prefill, sm_llm_forward_logits) append fp8 and run the chunk attention on a per-call bf16 expansion of the keys they see.  on = 0:
+ * more than one row (sm_llm_prefill, sm_llm_forward_logits) append fp8 and run the chunk attention on a per-call bf16 expansion of the keys they see (or, with
+ * sm_model_set_kv_fp8_chunk, on the codes themselves).  on = 0:
  * off (the default).  Call it before the first sm_stream_open.  SM_EINVAL for llm_fp16 models, a head_dim other than 128, on outside {0, 1}, and once a stream
  * has been opened (it stays locked after the last stream closes). */
 int sm_model_set_kv_fp8(sm_model* m, int on);
+/* kv_fp8 models: on = 1 runs the attention of calls with more than one row (sm_llm_prefill, sm_llm_forward_logits) through sm_llm_attention_fp8 on the cache's
+ * codes and scales instead of sm_kv_fp8_expand + the 16-bit chunk kernel: no capacity-sized bf16 K / V image per HIP stream (2 * cap * KV * 128 * 2 bytes), no
+ * stream synchronise when the cache grows; one fixed split workspace per HIP stream instead (16 * 32 * H * 130 floats, allocated by the first such call).  Made
+ * for short chunks against long contexts.  May be called at any time (the cache format does not change); on = 0: off, the default; one-row steps keep the decode
+ * kernel either way.  SM_EINVAL unless on is 0 or 1, and for on = 1 without sm_model_set_kv_fp8(m, 1). */
+int sm_model_set_kv_fp8_chunk(sm_model* m, int on);
 /* names of tensors still missing, '\n'-separated, into buf (for error messages) */
 int sm_model_missing(sm_model* m, char* buf, size_t buflen);
 

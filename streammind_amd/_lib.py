@@ -111,6 +111,7 @@ SIGNATURES = {
     "sm_llm_decode_attention_fp8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "sm_llm_decode_attention_fp8_tab": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "sm_kv_fp8_expand": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "sm_llm_attention_fp8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]),
     "sm_swiglu": (i32, [vp, i32, i32, vp, vp]),
     "sm_argmax": (i32, [vp, i32, vp, vp]),
     "sm_model_create": (i32, [C.POINTER(sm_config_t), C.POINTER(vp)]),
@@ -121,6 +122,7 @@ SIGNATURES = {
     "sm_model_set_weights_fp4": (i32, [vp, i32]),
     "sm_model_set_fp4_gemm": (i32, [vp, i32]),
     "sm_model_set_kv_fp8": (i32, [vp, i32]),
+    "sm_model_set_kv_fp8_chunk": (i32, [vp, i32]),
     "sm_model_missing": (i32, [vp, C.c_char_p, sz]),
     "sm_vit_encode": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "sm_vit_encode_pixels": (i32, [vp, vp, i32, i32, vp, vp, vp]),

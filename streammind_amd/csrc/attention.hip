@@ -1628,3 +1628,296 @@ extern "C" int sm_llm_decode_attention_fp8_tab(const void* q, const void* const*
     const SmDecodeSegTab tab = {(void* const*)kc_tab_dev, (void* const*)vtc_tab_dev, pos_dev, 0};
     return sm_llm_decode_attention_fp8_seg_tab(q, tab, S, nk_max, H, KV, dh, S_max, window, workspace, splits_max, ctx, stream);
 }
+
+// ------------------------------------------------------------------------------------------------ chunks of rows over the FP8 (e4m3) K / V cache
+// Causal attention of n >= 1 new rows at positions pos0 .. pos0 + n - 1 straight from the codes and scales (no bf16 expansion in front), with a work split made
+// for FEW queries against MANY keys.  The arithmetic is decode_attn_fp8_kernel's: codes -> bf16 in registers (exact), q bf16, bf16 x bf16 MFMA into fp32, the K
+// scale on the fp32 score, P' = bf16(e * vscale[key]) as the PV operand, the row sum over the unscaled rounded e.
+//   * a tile's 128 rows are (query, head of the group) pairs of ONE K / V group: row r = query r / G of the tile, head kvh * G + r % G (G = H / KV in {1, 2, 4, 8};
+//     128 / G consecutive queries).  One pass over a 64-key code tile serves every head of the group; wave w owns rows 32 w .. 32 w + 31 (consecutive queries, so
+//     its diagonal is short) and the softmax stays inside the wave: lane (i, g) owns the queries of columns i of the wave's two 16-row blocks.
+//   * grid = (query tile, K / V group, key split) flattened with the group fastest (KV = 8: a group's blocks share an XCD and its L2) and the LONGEST tiles first.
+//     Each tile's visible key range [window start & ~63, last query + 1) is cut into `splits` pieces of whole 64-key tiles; one split writes the bf16 context,
+//     more write fp32 (o, m, l) partials in attn_combine_kernel's layout (row = q * H + h); a piece past the range's end leaves (0, -inf, 0).
+//   * code tiles go global -> LDS by DMA (global_load_lds, 16 B per lane, double-buffered): 8 KiB of K codes (LDS row R of 128 B holds key
+//     (x >> 2) * 16 + a * 4 + (x & 3), a = R >> 4, x = R & 15 -- the decode kernel's permutation: a lane's sixteen scores are sixteen consecutive keys -- with the
+//     16-byte chunk index xor (R >> 1) & 7) and 8 KiB of V^T codes (row d of 64 B, chunk index xor (d >> 2) & 3), permutation and swizzles on the per-lane SOURCE
+//     address.  The tile's 64 K scales and 64 V scales land in a 512-byte LDS strip behind the codes by two 4-byte DMAs (waves 0 and 1): a lane fetches the
+//     sixteen of its keys with four 16-byte broadcast reads each, where the decode kernel's scales-in-lanes would take 32 cross-lane moves per wave and tile.
+//   * every wave converts the fragments it reads (v_cvt_scalef32_pk_bf16_fp8 between ds_read and MFMA): no bf16 image in LDS, 33 KiB of LDS per block.
+// Dead keys -- past pos0 + n inside the last tile, or in front of the earliest window start of the tile's queries -- may hold any bytes: their scores are SELECTED
+// to -inf, their scales and V codes to 0.  Keys masked for some rows only are live data and take the plain causal / window select.
+struct ChunkFp8P {
+    const bf16_t* q; bf16_t* ctx;               // [n][H*128]
+    const uint8_t* k; const uint8_t* vt;
+    int n, pos0, H, KV, S_max, window;
+    int g_shift;                                // log2(H / KV)
+    int nqt, splits;                            // query tiles of 128 >> g_shift queries; key splits
+    float* part_o; float* part_ml;              // splits > 1: [split][n * H][128], [split][n * H][2]
+    float c;
+};
+__global__ __launch_bounds__(256, 2) void chunk_attn_fp8_kernel(ChunkFp8P p) {
+    constexpr int DH = 128, KT = 8192, BUF = 2 * KT + 512;
+    __shared__ __attribute__((aligned(16))) char lds[2 * BUF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (wave in a scalar register: what hangs on it stays scalar)
+    const int i = lane & 15, g = lane >> 4;
+    const int L = blockIdx.x;
+    const int kvh = L % p.KV, z = (L / p.KV) % p.splits, qtile = p.nqt - 1 - L / (p.KV * p.splits);
+    const int gs = p.g_shift, tq0 = qtile * (128 >> gs);                // first query of the tile
+    const int nk = p.pos0 + p.n;
+    // this lane's two queries (a row past the chunk's end redoes the last query and stores nothing)
+    int qpos[2];
+    bf16x8 qf[2][4];                                                    // k-step kk*2 + hf: dims kk*64 + g*16 + hf*8 .. +7 (the order the K chunks are consumed in)
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const int row = wave * 32 + qb * 16 + i;
+        const int qi = tq0 + (row >> gs), qc = min(qi, p.n - 1);
+        qpos[qb] = p.pos0 + qc;
+        const bf16_t* src = p.q + ((size_t)qc * p.H + (kvh << gs) + (row & ((1 << gs) - 1))) * DH + g * 16;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qf[qb][s] = *(const bf16x8*)(src + (s >> 1) * 64 + (s & 1) * 8);
+    }
+    const int wq0 = tq0 + ((wave * 32) >> gs);
+    const bool active = wq0 < p.n;
+    const int pw_first = p.pos0 + wq0, pw_last = p.pos0 + min(tq0 + ((wave * 32 + 31) >> gs), p.n - 1);       // the wave's first and last query position
+    // the tile's key range and this block's piece of it
+    const int lo_min = p.window > 0 ? max(0, p.pos0 + tq0 - p.window + 1) : 0;                                 // earliest visible key of any query of the tile
+    const int k_end_t = p.pos0 + min(tq0 + (128 >> gs), p.n);
+    const int bps = (((k_end_t - (lo_min & ~63) + 63) >> 6) + p.splits - 1) / p.splits;                        // 64-key tiles per split
+    const int k_begin = (lo_min & ~63) + z * bps * 64, k_end = min(k_end_t, k_begin + bps * 64);
+
+    f32x4 o[2][8];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+        for (int df = 0; df < 8; ++df) o[qb][df] = f32x4{0, 0, 0, 0};
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+
+    // DMA sources = a scalar tile base that advances + a 32-bit per-lane offset that does not: wave w brings the 1-KiB pieces 2 w, 2 w + 1 of the K tile (8 permuted
+    // key rows each) and of the V^T tile (16 dims x 64 keys each); waves 0 / 1 the tile's K / V scales (lane L: key L)
+    const long k_rs = (long)p.KV * DH;
+    const size_t codes = (size_t)p.S_max * p.KV * DH;
+    const uint8_t* kt = p.k + kvh * DH + (long)k_begin * k_rs;
+    const uint8_t* vtt = p.vt + (size_t)kvh * DH * p.S_max + k_begin;
+    const float* sct = wave == 0 ? (const float*)(p.k + codes) + (size_t)k_begin * p.KV + kvh : (const float*)(p.vt + codes) + (size_t)kvh * p.S_max + k_begin;
+    const int sadv = wave == 0 ? 64 * p.KV : 64;
+    const uint32_t soff = lane * (wave == 0 ? p.KV : 1);
+    uint32_t koff[2], voff[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int P = wave * 2 + j;
+        const int R = P * 8 + (lane >> 3), a = R >> 4, x = R & 15;
+        koff[j] = (uint32_t)(((x >> 2) * 16 + a * 4 + (x & 3)) * (int)k_rs + (((lane & 7) ^ ((R >> 1) & 7)) * 16));
+        const int d = P * 16 + (lane >> 2);
+        voff[j] = (uint32_t)(d * p.S_max + (((lane & 3) ^ ((d >> 2) & 3)) * 16));
+    }
+    auto issue = [&](int bufi) {                  // a tile never runs past the cache: S_max is a multiple of 64
+        char* Kl = lds + bufi * BUF;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            __builtin_amdgcn_global_load_lds((gbl_ptr_a)(kt + koff[j]), (lds_ptr_a)(Kl + (wave * 2 + j) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_ptr_a)(vtt + voff[j]), (lds_ptr_a)(Kl + KT + (wave * 2 + j) * 1024), 16, 0, 0);
+        }
+        if (wave < 2) __builtin_amdgcn_global_load_lds((gbl_ptr_a)(sct + soff), (lds_ptr_a)(Kl + 2 * KT + wave * 256), 4, 0, 0);
+        kt += 64 * k_rs;
+        vtt += 64;
+        sct += sadv;
+    };
+    if (k_begin < k_end) issue(0);
+    int buf = 0;
+    for (int kt0 = k_begin; kt0 < k_end; kt0 += 64) {
+        const char* Kl = lds + buf * BUF;
+        const char* Vl = Kl + KT;
+        const char* Sl = Vl + KT;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                  // every wave's pieces of this tile have landed; everyone is done with the other buffer
+        if (kt0 + 64 < k_end) issue(buf ^ 1);
+        buf ^= 1;
+        // (wave-uniform) nothing of this tile is visible to the wave: past its last query, or in front of its first query's window
+        if (!active || kt0 > pw_last || (p.window > 0 && kt0 + 64 <= pw_first - p.window + 1)) continue;
+        // ---- S^T = K . Q^T: fragment a of lane (i, g) = keys kt0 + g*16 + a*4 + 0..3
+        u32x4 kq[4][2];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int rho = a * 16 + i;
+                kq[a][kk] = *(const u32x4*)(Kl + rho * 128 + (((kk * 4 + g) ^ ((rho >> 1) & 7)) * 16));
+            }
+        float s[2][16];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    const bf16x8 kf = kv8_to_bf16(kq[a][kk][hf * 2], kq[a][kk][hf * 2 + 1]);
+                    a0 = mfma16<false>(kf, qf[0][kk * 2 + hf], a0);
+                    a1 = mfma16<false>(kf, qf[1][kk * 2 + hf], a1);
+                }
+            const f32x4 kv = *(const f32x4*)(Sl + (g * 16 + a * 4) * 4);       // the K scales of these four keys multiply the fp32 scores
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { s[0][a * 4 + r] = a0[r] * kv[r]; s[1][a * 4 + r] = a1[r] * kv[r]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);        // (the K fragments are dead before the V fragments take their registers)
+        // ---- the V^T fragments (keys g*16 .. +15 of dim df*16 + i) and the V scales of this lane's sixteen keys
+        u32x4 vq[8];
+#pragma unroll
+        for (int df = 0; df < 8; ++df) {
+            const int d = df * 16 + i;
+            vq[df] = *(const u32x4*)(Vl + d * 64 + ((g ^ ((d >> 2) & 3)) * 16));
+        }
+        const int kb = kt0 + g * 16;                                    // this lane's sixteen keys: kb + j
+        const bool has_dead = kt0 + 64 > nk || kt0 < lo_min;            // (block-uniform) only the last tile of the cache and the first of a window
+        if (has_dead) {
+            uint32_t keep[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const bool dead = kb + j >= nk || kb + j < lo_min;
+                keep[j >> 2] |= dead ? 0u : (0xffu << (8 * (j & 3)));
+            }
+#pragma unroll
+            for (int df = 0; df < 8; ++df)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) vq[df][w] &= keep[w];
+        }
+        // (wave-uniform) the causal / window select runs only where the tile reaches past the wave's first query or in front of its last query's window
+        const bool edge = has_dead || kt0 + 63 > pw_first || (p.window > 0 && kt0 < pw_last - p.window + 1);
+        bf16x8 pf[2][2];
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+            float* sq = s[qb];
+            if (edge) {                           // (a dead key's score may be NaN here -- NaN codes, a NaN scale: it is selected away, like the masked ones)
+                const int lo = p.window > 0 ? max(qpos[qb] - p.window + 1, lo_min) : lo_min;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) sq[j] = (kb + j > qpos[qb] || kb + j < lo) ? -INFINITY : sq[j];
+            }
+            float mx = sq[0];
+#pragma unroll
+            for (int j = 1; j < 16; ++j) mx = fmaxf(mx, sq[j]);
+            mx = xor32_max(xor16_max(mx));
+            const float m_new = fmaxf(m_run[qb], mx);
+            const float mc = (m_new == -INFINITY ? 0.f : m_new) * p.c;              // a row that has seen no key yet keeps m = -inf: guard the subtraction
+            const bool moved = m_new != m_run[qb];
+            const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run[qb], p.c, -mc));
+            m_run[qb] = m_new;
+            float psum = 0.f;
+#pragma unroll
+            for (int hk = 0; hk < 2; ++hk) {      // keys kb + 8 hk .. + 7: one PV operand.  Their V scales come from the strip for each of the two queries (broadcast reads;
+                float pe[8];                      // sixteen scales held across both softmaxes cost the registers that keep the kernel out of scratch)
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    f32x4 vv = *(const f32x4*)(Sl + 256 + (g * 16 + hk * 8 + a * 4) * 4);
+                    if (has_dead) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const int key = kb + hk * 8 + a * 4 + r; vv[r] = (key >= nk || key < lo_min) ? 0.f : vv[r]; }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r += 2) {
+                        const int j = hk * 8 + a * 4 + r;
+                        const float e0 = __builtin_amdgcn_exp2f(fmaf(sq[j], p.c, -mc)), e1 = __builtin_amdgcn_exp2f(fmaf(sq[j + 1], p.c, -mc));
+                        const uint32_t er = pack2bf(e0, e1);                         // the row sum adds the rounded, unscaled e
+                        psum += __uint_as_float(er << 16) + __uint_as_float(er & 0xffff0000u);
+                        pe[a * 4 + r] = e0 * vv[r];                                  // the V scale rides in P, folded in before the one rounding to bf16
+                        pe[a * 4 + r + 1] = e1 * vv[r + 1];
+                    }
+                }
+                pf[qb][hk] = make8<false>(pe);
+            }
+            if (__builtin_amdgcn_ballot_w64(moved) != 0) {
+#pragma unroll
+                for (int df = 0; df < 8; ++df) o[qb][df] *= alpha;
+                l_run[qb] *= alpha;
+            }
+            l_run[qb] += psum;
+            __builtin_amdgcn_sched_barrier(0);    // (one query block's softmax at a time: interleaved, the two spill)
+        }
+        // ---- O^T += V^T . P'^T: bytes 0..7 / 8..15 of a V fragment against P' of the lane's keys 0..7 / 8..15
+#pragma unroll
+        for (int df = 0; df < 8; ++df) {
+            const bf16x8 v0 = kv8_to_bf16(vq[df][0], vq[df][1]), v1 = kv8_to_bf16(vq[df][2], vq[df][3]);
+            o[0][df] = mfma16<false>(v0, pf[0][0], o[0][df]);
+            o[1][df] = mfma16<false>(v0, pf[1][0], o[1][df]);
+            o[0][df] = mfma16<false>(v1, pf[0][1], o[0][df]);
+            o[1][df] = mfma16<false>(v1, pf[1][1], o[1][df]);
+        }
+    }
+    // ---- store: lane (i, g) holds d = df*16 + g*4 + 0..3 of its two queries; the row sum is still split over the four g's.  The output rows are worked out again
+    // from a lane id the compiler cannot trace back (as common subexpressions of the prologue they sat in registers through the whole loop -- and spilled)
+    int lane2 = lane;
+    asm volatile("" : "+v"(lane2));
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const float l = xor32_sum(xor16_sum(l_run[qb]));
+        const int row = wave * 32 + qb * 16 + (lane2 & 15), qi = tq0 + (row >> gs);
+        if (qi >= p.n) continue;
+        const size_t orow = (size_t)qi * p.H + (kvh << gs) + (row & ((1 << gs) - 1));
+        if (p.splits == 1) {
+            const float inv = 1.0f / l;
+            bf16_t* dst = p.ctx + orow * DH + (lane2 >> 4) * 4;
+#pragma unroll
+            for (int df = 0; df < 8; ++df) {
+                const f32x4 v = o[qb][df] * inv;
+                *(u32x2*)(dst + df * 16) = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+            }
+        } else {
+            const size_t prow = (size_t)z * p.n * p.H + orow;
+            float* dst = p.part_o + prow * DH + (lane2 >> 4) * 4;
+#pragma unroll
+            for (int df = 0; df < 8; ++df) *(f32x4*)(dst + df * 16) = o[qb][df];
+            if (lane2 < 16) *(f32x2*)(p.part_ml + prow * 2) = f32x2{m_run[qb], l};
+        }
+    }
+}
+
+// key splits of a launch: none while the (query tile, K / V group) blocks fill half the chip by themselves; else one block per CU, at least four 64-key tiles per
+// split (a split's fp32 partial costs a block about what one key tile does), at most what the workspace holds and 64 (attn_combine_kernel: one split per lane)
+static int chunk_fp8_splits(int nqt, int KV, int nk_tiles, size_t rows, size_t workspace_floats, int dh) {
+    static std::atomic<int> n_cu{0};
+    int cu = n_cu.load(std::memory_order_relaxed);
+    if (!cu) {
+        int dev = 0; hipDeviceProp_t prop;
+        cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        n_cu.store(cu, std::memory_order_relaxed);
+    }
+    long sp = cu / (nqt * KV);
+    if (sp > nk_tiles / 4) sp = nk_tiles / 4;
+    const size_t cap = workspace_floats / (rows * (dh + 2));
+    if ((size_t)sp > cap) sp = (long)cap;
+    if (sp > 64) sp = 64;
+    return sp < 1 ? 1 : (int)sp;
+}
+extern "C" int sm_llm_attention_fp8(const void* q, const void* kcache, const void* vtcache, int n, int pos0, int H, int KV, int dh, int S_max, int window,
+                                    float* workspace, size_t workspace_floats, void* ctx, void* stream) {
+    SM_REQUIRE(q && kcache && vtcache && ctx && n > 0 && pos0 >= 0 && window >= 0 && H > 0 && KV > 0, "sm_llm_attention_fp8: bad args");
+    SM_REQUIRE(dh == 128, "sm_llm_attention_fp8: the fp8 K / V cache takes head_dim 128 only (got %d)", dh);
+    SM_REQUIRE(H % KV == 0, "sm_llm_attention_fp8: H %% KV (H = %d, KV = %d)", H, KV);
+    const int G = H / KV;
+    SM_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "sm_llm_attention_fp8: H / KV = %d (1, 2, 4 or 8 query heads per K / V head)", G);
+    SM_REQUIRE(S_max > 0 && S_max % 64 == 0, "sm_llm_attention_fp8: S_max %% 64 (got %d)", S_max);
+    SM_REQUIRE(pos0 + n <= S_max, "sm_llm_attention_fp8: pos0 + n <= S_max (pos0 = %d, n = %d, S_max = %d)", pos0, n, S_max);
+    SM_REQUIRE((((uintptr_t)q | (uintptr_t)kcache | (uintptr_t)vtcache | (uintptr_t)ctx | (uintptr_t)workspace) & 15) == 0, "sm_llm_attention_fp8: q, ctx, the caches and the workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    ChunkFp8P p;
+    p.q = (const bf16_t*)q; p.ctx = (bf16_t*)ctx; p.k = (const uint8_t*)kcache; p.vt = (const uint8_t*)vtcache;
+    p.n = n; p.pos0 = pos0; p.H = H; p.KV = KV; p.S_max = S_max; p.window = window;
+    p.g_shift = G == 1 ? 0 : G == 2 ? 1 : G == 4 ? 2 : 3;
+    p.nqt = cdiv(n, 128 / G);
+    // the longest key range a tile walks: the last tile's, from the 64-key tile of its first query's window start to the newest key
+    const int lo = window > 0 ? (pos0 + (p.nqt - 1) * (128 / G) - window + 1 > 0 ? (pos0 + (p.nqt - 1) * (128 / G) - window + 1) & ~63 : 0) : 0;
+    const size_t rows = (size_t)n * H;
+    p.splits = workspace ? chunk_fp8_splits(p.nqt, KV, cdiv(pos0 + n - lo, 64), rows, workspace_floats, dh) : 1;
+    p.part_o = workspace; p.part_ml = workspace ? workspace + (size_t)p.splits * rows * dh : nullptr;
+    p.c = (1.0f / sqrtf((float)dh)) * 1.4426950408889634f;
+    {
+        SmProfScope prof(SM_PROF_ATTN, st);
+        chunk_attn_fp8_kernel<<<dim3((unsigned)(p.nqt * KV * p.splits)), 256, 0, st>>>(p);
+        SM_LAUNCH_CHECK();
+    }
+    if (p.splits > 1) {
+        attn_combine_kernel<<<dim3((unsigned)rows, 1), 64, 0, st>>>(p.part_o, p.part_ml, p.splits, (int)rows, dh, p.c, p.ctx, 0, 0, 0);
+        SM_LAUNCH_CHECK();
+    }
+    return SM_OK;
+}

@@ -180,5 +180,6 @@ __host__ __device__ __forceinline__ size_t fp4_rg_bytes(int KS) { return (size_t
 //               scales [KV][cap] fp32       at byte offset KV * 128 * cap
 //   one scale per (token, KV head) row of 128 values: amax / 448, 1.0 when amax == 0; code = RNE(x / scale) saturated at +-448 (the NaN codes 0x7F / 0xFF are never
 //   written).  2112 bytes per token and layer at KV = 8 instead of 4096.  Producers: kv_fp8.hip; consumers: decode_attn_fp8_kernel (attention.hip, reads the codes in
-//   MFMA operand order) and kv_fp8_expand_kernel (kv_fp8.hip: codes * scale -> bf16 for the chunk attention kernels).
+//   MFMA operand order), kv_fp8_expand_kernel (kv_fp8.hip: codes * scale -> bf16 for the 16-bit chunk attention kernels) and chunk_attn_fp8_kernel (attention.hip:
+//   chunks of rows straight from the codes, sm_model_set_kv_fp8_chunk).
 __host__ __device__ __forceinline__ size_t kv_fp8_buf_bytes(int cap, int KV) { return (size_t)cap * KV * 128 + (size_t)cap * KV * 4; }

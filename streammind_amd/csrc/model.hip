@@ -137,6 +137,7 @@ struct sm_model {
     bool fp4_gemm = false;         // sm_model_set_fp4_gemm: mode 2's slots go out as SM_W_FP4_GEMM (the tiled fp4 GEMM above 128 rows)
     bool any_loaded = false;       // a tensor has been handed over: the weight formats are fixed from here on
     bool kv_fp8 = false;           // sm_model_set_kv_fp8: streams hold e4m3 K / V caches with one fp32 scale per (token, KV head) (format: common.h)
+    bool kv_fp8_chunk = false;     // sm_model_set_kv_fp8_chunk: calls with more than one row read the fp8 cache directly (sm_llm_attention_fp8) instead of a bf16 expansion
     int streams_opened = 0;        // the cache format is fixed once a stream has been opened (never counted down: a stream may outlive its model's handle in a
                                    // host binding, so closing one does not touch the model; the switch stays locked after the last stream closes)
     std::unordered_map<std::string, Slot> slots;           // canonical name -> storage
@@ -177,7 +178,9 @@ struct sm_model {
     // carries from call to call (pending token, last logits, K / V, frame tokens, Mamba state) stays in the stream -- so streams driven on one HIP stream
     // share a set in stream order, and a reply on the LLM lane (its own HIP stream) has its own.
     struct LlmWs { DevBuf emb, xnb, qkvf, qb, ctxb, actb, attn_ws;
-                   DevBuf kexp, vtexp; };     // fp8 K / V cache: the bf16 expansion a chunk call's attention reads (K [cap][kn], V^T [kn][cap]; kv_fp8_scratch)
+                   DevBuf kexp, vtexp;        // fp8 K / V cache: the bf16 expansion a chunk call's attention reads (K [cap][kn], V^T [kn][cap]; kv_fp8_scratch)
+                   DevBuf chunk_ws; };        // kv_fp8_chunk instead: the key-split partials of sm_llm_attention_fp8, KV_FP8_CHUNK_WS_ROWS rows of (dh + 2) floats per head
+    static constexpr int KV_FP8_CHUNK_WS_ROWS = 16 * 32;       // 16 splits of a 32-token chunk (8.5 MB at 32 heads of 128); fewer splits above that, never a larger buffer
     static constexpr int LLM_CHUNK = 2048;          // rows of a prefill / teacher-forced chunk
     std::map<void*, std::unique_ptr<LlmWs>> llm_ws;
     int llm_workspace(void* stream, LlmWs** out) {
@@ -625,9 +628,19 @@ extern "C" int sm_model_set_kv_fp8(sm_model* m, int on) {
     SM_REQUIRE(!on || !m->c.llm_fp16, "sm_model_set_kv_fp8: exclusive with llm_fp16 (the fp8 cache feeds bf16 operands)");
     SM_REQUIRE(!on || (m->c.llm_layers > 0 && m->c.llm_heads > 0 && m->c.llm_hidden / m->c.llm_heads == 128), "sm_model_set_kv_fp8: the fp8 K / V cache takes head_dim 128 only");
     m->kv_fp8 = on != 0;
+    if (!on) m->kv_fp8_chunk = false;
     return SM_OK;
 }
 // mode 2 only: prefill chunks above 128 rows on the tiled fp4 GEMM (SM_W_FP4_GEMM) instead of the per-call expansion.  Same window as the setter above.
+// kv_fp8 only: chunk calls on the fused chunk attention over the codes (chunk_attn_fp8_kernel) instead of expansion + 16-bit kernel.  Any time: the cache format
+// does not change, the choice is made per call.
+extern "C" int sm_model_set_kv_fp8_chunk(sm_model* m, int on) {
+    SM_REQUIRE(m, "sm_model_set_kv_fp8_chunk: null model");
+    SM_REQUIRE(on == 0 || on == 1, "sm_model_set_kv_fp8_chunk: on = %d (0 or 1)", on);
+    SM_REQUIRE(!on || m->kv_fp8, "sm_model_set_kv_fp8_chunk: needs sm_model_set_kv_fp8(m, 1) first");
+    m->kv_fp8_chunk = on != 0;
+    return SM_OK;
+}
 extern "C" int sm_model_set_fp4_gemm(sm_model* m, int on) {
     SM_REQUIRE(m && !m->any_loaded && !m->finalized, "sm_model_set_fp4_gemm: call it between sm_model_create and the first sm_model_load_tensor");
     SM_REQUIRE(on == 0 || on == 1, "sm_model_set_fp4_gemm: on = %d (0 or 1)", on);
@@ -1485,6 +1498,8 @@ static int llm_layers(sm_stream* s, sm_model::LlmWs* W, int n, void* stream) {
             if ((rc = sm_rope_kv_append_fp8(W->qkvf.as<float>(), n, s->kv_len, H, KV, dh, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p, s->kc[l].p, s->vtc[l].p, s->cap, stream))) return rc;
             if (n == 1) {
                 if ((rc = sm_llm_decode_attention_fp8(W->qb.p, s->kc[l].p, s->vtc[l].p, s->kv_len, H, KV, dh, s->cap, c.llm_sliding_window, W->attn_ws.as<float>(), SM_DECODE_SPLITS, W->ctxb.p, stream))) return rc;
+            } else if (m->kv_fp8_chunk) {
+                if ((rc = sm_llm_attention_fp8(W->qb.p, s->kc[l].p, s->vtc[l].p, n, s->kv_len, H, KV, dh, s->cap, c.llm_sliding_window, W->chunk_ws.as<float>(), W->chunk_ws.bytes / 4, W->ctxb.p, stream))) return rc;
             } else {
                 SM_REQUIRE(W->kexp.bytes >= (size_t)s->cap * kn * 2, "llm_layers: the fp8 cache's expansion scratch is smaller than the stream's capacity %d", s->cap);
                 const int k_lo = c.llm_sliding_window > 0 ? (s->kv_len - c.llm_sliding_window + 1 > 0 ? (s->kv_len - c.llm_sliding_window + 1) & ~63 : 0) : 0;
@@ -1561,12 +1576,15 @@ static int llm_head(sm_stream* s, sm_model::LlmWs* W, int row, void* stream, int
 static int kv_fp8_scratch(sm_stream* s, sm_model::LlmWs* W, void* stream) {
     if (!s->m->kv_fp8) return SM_OK;
     const sm_config_t& c = s->m->c;
-    const size_t need = (size_t)s->cap * c.llm_kv_heads * (c.llm_hidden / c.llm_heads) * 2;
-    if (W->kexp.bytes >= need) return SM_OK;
+    // kv_fp8_chunk: no expansion; the split workspace of the fused kernel has one size, so only the call that creates it passes this point
+    const bool fused = s->m->kv_fp8_chunk;
+    const size_t need = fused ? (size_t)sm_model::KV_FP8_CHUNK_WS_ROWS * c.llm_heads * (c.llm_hidden / c.llm_heads + 2) * 4 : (size_t)s->cap * c.llm_kv_heads * (c.llm_hidden / c.llm_heads) * 2;
+    if ((fused ? W->chunk_ws.bytes : W->kexp.bytes) >= need) return SM_OK;
     hipStream_t st = (hipStream_t)stream;
     {   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess) SM_REQUIRE(cs == hipStreamCaptureStatusNone, "kv_fp8_scratch: the expansion scratch must grow to %d tokens but the HIP stream is capturing", s->cap);
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess) SM_REQUIRE(cs == hipStreamCaptureStatusNone, "kv_fp8_scratch: the chunk attention's scratch must be allocated (cache capacity %d tokens) but the HIP stream is capturing", s->cap);
         else (void)hipGetLastError(); }
+    if (fused) return W->chunk_ws.alloc(need);   // created once, never replaced: nothing enqueued can be reading an older one
     SM_HIP(hipStreamSynchronize(st));            // the old scratch may still be read by kernels enqueued before this call
     int rc;
     if ((rc = W->kexp.alloc(need, true)) || (rc = W->vtexp.alloc(need, true))) return rc;

@@ -97,7 +97,7 @@ def path_config_from_checkpoint(cfgj: dict, vision_cfg: dict, **overrides) -> Pa
 def load_pretrained_model(model_path, model_base=None, model_name="VideoLLaMA2-7B", load_8bit=False, load_4bit=False,
                           device_map="auto", device="cuda", use_flash_attn=False, **kwargs):
     """-> (tokenizer, model, image_processor, context_len).  Extra keyword arguments of this build: max_frames_per_call
-    (ViT batch capacity, default 8), max_seq (KV capacity per stream), max_frames (token store), weights_fp8, weights_fp4, fp4_gemm (with weights_fp4=2: prefill chunks above 128 rows on the tiled fp4 GEMM), kv_fp8 (the K / V cache as e4m3 codes with one scale per token and KV head: half the cache bytes; bf16 operands for the LLM, head_dim 128), torch_dtype
+    (ViT batch capacity, default 8), max_seq (KV capacity per stream), max_frames (token store), weights_fp8, weights_fp4, fp4_gemm (with weights_fp4=2: prefill chunks above 128 rows on the tiled fp4 GEMM), kv_fp8 (the K / V cache as e4m3 codes with one scale per token and KV head: half the cache bytes; bf16 operands for the LLM, head_dim 128), kv_fp8_chunk (with kv_fp8: prefill and teacher-forced chunks read the codes directly instead of a per-call bf16 expansion), torch_dtype
     (torch.float16 = the reference's loading precision, default; torch.bfloat16 = its evaluation precision)."""
     if load_8bit or load_4bit:
         raise NotImplementedError("bitsandbytes quantisation is not part of the MI355X path")
@@ -134,7 +134,10 @@ def load_pretrained_model(model_path, model_base=None, model_name="VideoLLaMA2-7
     if g4 and w4 != 2:
         raise ValueError("fp4_gemm requires weights_fp4=2")
     k8 = bool(kwargs.pop("kv_fp8", False))                  # fp8 K / V cache: bf16 operands for the LLM, as with the quantised weights
-    over = dict(max_frames_per_call=kwargs.pop("max_frames_per_call", 8), weights_fp8=w8, weights_fp4=w4, fp4_gemm=g4, kv_fp8=k8, llm_fp16=(tdt == torch.float16 and not w8 and not w4 and not k8), proj_fp16=(tdt == torch.float16 and not w8),
+    k8c = bool(kwargs.pop("kv_fp8_chunk", False))
+    if k8c and not k8:
+        raise ValueError("kv_fp8_chunk requires kv_fp8=True")
+    over = dict(max_frames_per_call=kwargs.pop("max_frames_per_call", 8), weights_fp8=w8, weights_fp4=w4, fp4_gemm=g4, kv_fp8=k8, kv_fp8_chunk=k8c, llm_fp16=(tdt == torch.float16 and not w8 and not w4 and not k8), proj_fp16=(tdt == torch.float16 and not w8),
                 vit_fp16=(tdt == torch.float16 and vj.get("vision_config", vj)["hidden_size"] // vj.get("vision_config", vj)["num_attention_heads"] == 64))
     ppath = os.path.join(tower_dir, "preprocessor_config.json")
     if os.path.exists(ppath):                               # the normalisation constants belong to the tower checkpoint

@@ -64,6 +64,7 @@ class PathConfig:
                                    # the setter's mode: True / 1 = expansion above 16 rows, 2 = the fp4 weight stream up to 128 rows (group decode up to 128 streams)
     fp4_gemm: bool = False         # opt-in, needs weights_fp4 = 2: prefill chunks above 128 rows on the tiled fp4 GEMM instead of the per-call expansion (sm_model_set_fp4_gemm)
     kv_fp8: bool = False           # opt-in: the LLM's K / V cache as e4m3 codes + one fp32 scale per (token, KV head) (sm_model_set_kv_fp8; head_dim 128, exclusive with llm_fp16)
+    kv_fp8_chunk: bool = False     # opt-in, needs kv_fp8: prefill / teacher-forced chunks read the fp8 cache directly (fused chunk attention, sm_model_set_kv_fp8_chunk) instead of a bf16 expansion
     vit_fp16: bool = False         # vision-tower operands in IEEE fp16 (the reference demo's precision) instead of bf16
     llm_fp16: bool = False         # the same for the LLM (weights, embedding table, activations, q / KV caches, attention P)
     proj_fp16: bool = False        # the same for the connector + gate weights (activations as fp16 hi/lo pairs in precise mode)
@@ -126,6 +127,8 @@ class NativeModel:
             check(self.lib.sm_model_set_fp4_gemm(self.h, 1), "sm_model_set_fp4_gemm")
         if getattr(cfg, "kv_fp8", False):            # the cache format of the model's streams: before the first open_stream
             check(self.lib.sm_model_set_kv_fp8(self.h, 1), "sm_model_set_kv_fp8")
+        if getattr(cfg, "kv_fp8_chunk", False):      # on top of kv_fp8 (the setter refuses it otherwise)
+            check(self.lib.sm_model_set_kv_fp8_chunk(self.h, 1), "sm_model_set_kv_fp8_chunk")
         self.finalized = False
         self.ignored = []
 

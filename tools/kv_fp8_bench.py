@@ -6,6 +6,10 @@ prints one JSON line:
   prefill2048_tok_s tokens/s of a 2048-token prefill into an empty stream, 12 prefills per window (~0.35 s; the fp8 leg pays the quantising append and the
                     per-layer expansion)
   kv_bytes_stream   sm_stream_kv_bytes of a stream holding 336 tokens
+  chunk_attn_us     (fp8 cache only) HIP-event time of one layer's chunk attention work at H = 32, KV = 8, capacity 4096, per (n, pos0): `expand_bf16` = what
+                    llm_layers issues with kv_fp8_chunk off (sm_kv_fp8_expand over the visible keys + the 16-bit chunk kernel), `expand_only` = that expansion
+                    alone, `fused` = with the switch on (sm_llm_attention_fp8 incl. its split merge); 200 calls per bracket (50 from 512 rows), the three alternating over the rounds
+  prefill2048_tok_s_chunk  the fp8 leg's 2048-token prefill with kv_fp8_chunk on
 
     python tools/kv_fp8_bench.py [rounds]"""
 import ctypes as C
@@ -34,6 +38,41 @@ def attn_us(m, run, steps):
     cnt, ms = C.c_int(), C.c_float()
     m.lib.sm_prof_read(2, C.byref(cnt), C.byref(ms))
     return ms.value * 1e3 / max(cnt.value, 1)
+
+
+CHUNK_POINTS = ((16, 4080), (64, 4032), (512, 1536), (2048, 0))
+
+
+def chunk_attn_us(lib, rounds):
+    H, KV, cap, nc = 32, 8, 4096, 4096 * 8 * 128
+    g = torch.Generator(device="cuda").manual_seed(3)
+    kb, vb = (torch.randint(0, 0x78, (cap * KV * 132,), dtype=torch.uint8, device="cuda", generator=g) for _ in range(2))      # finite codes, scales 2^-6
+    for b in (kb, vb):
+        b[nc:].view(torch.float32).fill_(2.0 ** -6)
+    q = torch.randn(2048, H * 128, device="cuda", generator=g).bfloat16()
+    ctx, kx, vx, ws = torch.empty_like(q), torch.zeros(nc, dtype=torch.bfloat16, device="cuda"), torch.zeros(nc, dtype=torch.bfloat16, device="cuda"), torch.empty(16 * 32 * H * 130, device="cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = lambda t: C.c_void_p(t.data_ptr())
+
+    def legs(n, pos0):
+        expand = lambda: lib.sm_kv_fp8_expand(P(kb), P(vb), 0, pos0 + n, KV, 128, cap, P(kx), P(vx), st)
+        return {"expand_bf16": lambda: expand() or lib.sm_llm_attention(P(q), P(kx), P(vx), n, pos0, H, KV, 128, cap, P(ctx), st), "expand_only": expand,
+                "fused": lambda: lib.sm_llm_attention_fp8(P(q), P(kb), P(vb), n, pos0, H, KV, 128, cap, 0, P(ws), ws.numel(), P(ctx), st)}
+
+    out = {}
+    for n, pos0 in CHUNK_POINTS:
+        per, iters = {name: [] for name in legs(n, pos0)}, (200 if n <= 64 else 50)          # windows of 10 ms and more
+        for _ in range(rounds):
+            for name, fn in legs(n, pos0).items():
+                assert fn() == 0
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record(); torch.cuda.synchronize()
+                per[name].append(round(e0.elapsed_time(e1) * 1e3 / iters, 2))
+        out[f"{n}@{pos0}"] = {name: {"median": statistics.median(v), "runs": v} for name, v in per.items()}
+    return out
 
 
 def main(rounds=3):
@@ -86,11 +125,22 @@ def main(rounds=3):
                 st.prefill(p); st.set_kv_len(0)
             torch.cuda.synchronize()
             res[name]["prefill2048_tok_s"].append(round(12 * 2048 / (time.perf_counter() - t0), 1))
+            if name == "fp8":                            # the same prefill with the fused chunk attention (the switch may be thrown at any time)
+                assert m.lib.sm_model_set_kv_fp8_chunk(m.h, 1) == 0
+                st.prefill(p); st.set_kv_len(0); torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(12):
+                    st.prefill(p); st.set_kv_len(0)
+                torch.cuda.synchronize()
+                res[name].setdefault("prefill2048_tok_s_chunk", []).append(round(12 * 2048 / (time.perf_counter() - t0), 1))
+                assert m.lib.sm_model_set_kv_fp8_chunk(m.h, 0) == 0
             st.close()
     for name in legs:
         res[name]["decode_attn_us"]["1x4096"] = {"median": round(statistics.median(per[name]), 2), "runs": [round(v, 2) for v in per[name]]}
-        for k in ("group512_ms_step", "prefill2048_tok_s"):
-            res[name][k] = {"median": statistics.median(res[name][k]), "runs": res[name][k]}
+        for k in ("group512_ms_step", "prefill2048_tok_s", "prefill2048_tok_s_chunk"):
+            if k in res[name]:
+                res[name][k] = {"median": statistics.median(res[name][k]), "runs": res[name][k]}
+    res["fp8"]["chunk_attn_us"] = chunk_attn_us(legs["fp8"][1].lib, rounds)
     print(json.dumps({"kv_fp8_bench": res, "rounds": rounds}))
 
 
