@@ -319,6 +319,25 @@ int sm_kv_fp8_expand(const void* kcache, const void* vtcache, int k_lo, int k_hi
  * S_max % 64 != 0, pos0 + n > S_max. */
 int sm_llm_attention_fp8(const void* q_bf16, const void* kcache, const void* vtcache, int n, int pos0, int H, int KV, int dh, int S_max, int window,
                          float* workspace, size_t workspace_floats, void* ctx_bf16, void* stream);
+/* ragged causal attention over the 16-bit caches of S streams: the `rows` query rows of q [rows][H*dh] (bf16, or IEEE fp16 with f16 != 0) belong to S streams --
+ * stream s owns rows row0_s .. row0_s + n_s - 1, which sit (already appended) at positions pos0_s .. of ITS cache K [cap_s][KV*dh], V^T [KV*dh][cap_s]; ctx
+ * [rows][H*dh] in the operand type, rows of no stream are left unspecified.  kc_tab_dev / vtc_tab_dev: device arrays of the S cache pointers; seg_dev: device
+ * int32 [S][4] = (row0, n, pos0, cap), ascending and disjoint in row0; work_dev / n_work / splits: what sm_llm_attention_ragged_plan made of the same seg values
+ * on the host (work items = (stream, tile of 128 / (H / KV) queries), longest visible key range first; one key-split count for the launch, chosen as
+ * sm_llm_attention_fp8 chooses it with all items in the place of one chunk's tiles).  workspace: fp32, splits * rows * H * (dh + 2) floats when splits > 1.
+ * dh 128, H / KV in {1, 2, 4, 8}, window as sm_llm_attention_window.  Cache positions >= pos0_s + n_s and, with a window, < pos0_s - window + 1 may hold any
+ * bytes.  With S = 1 it is the short-chunk / long-context form of sm_llm_attention (key splits instead of one block per head walking every key). */
+int sm_llm_attention_ragged_plan(const int32_t* seg_host, int S, int rows, int H, int KV, int window, size_t workspace_floats, int32_t* work_host,
+                                 int max_items, int* n_work, int* splits);
+int sm_llm_attention_ragged(const void* q, const void* const* kc_tab_dev, const void* const* vtc_tab_dev, const int32_t* seg_dev, const int32_t* work_dev,
+                            int n_work, int rows, int H, int KV, int dh, int window, int f16, float* workspace, size_t workspace_floats, int splits,
+                            void* ctx, void* stream);
+/* sm_rope_kv_append for the rows of S streams in one launch (head_dim 128; 16-bit caches, IEEE fp16 with f16 != 0): qkv fp32 [rows][(H+2KV)*128], q
+ * [rows][H*128]; stream s's rows (seg_dev as above) are rotated at positions pos0_s .. and appended to kc_tab_dev[s] / vtc_tab_dev[s] (pitch cap_s).  tiles_dev:
+ * int32 [n_tiles][2] = (stream, first row of a 64-row tile of that stream's rows), every tile of every stream once.  Bytes written are those of
+ * sm_rope_kv_append per stream. */
+int sm_rope_kv_append_ragged(const float* qkv, const int32_t* seg_dev, const int32_t* tiles_dev, int n_tiles, int H, int KV, const float* cos_tab,
+                             const float* sin_tab, void* q, void* const* kc_tab_dev, void* const* vtc_tab_dev, int f16, void* stream);
 /* out[m] = bf16( silu(gu[m][0:F]) * gu[m][F:2F] ) */
 int sm_swiglu(const float* gu, int M, int F, void* out_bf16, void* stream);
 /* greedy argmax over fp32 logits[V] -> token (int32, device) ; first max wins (torch.argmax)           */
@@ -580,6 +599,15 @@ int sm_group_push_pooled(sm_stream_group* g, const float* pooled, int F, float* 
  * generate loops (videollama2_mistral.py:426-431; "only support batch size 1"): batch-1 decode is bound by streaming 14.2 GB
  * of weights per token, which S streams share here. */
 int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_host, int n_steps, int32_t* out_ids_dev, void* stream);
+/* batched ragged prefill: counts_host[i] new ids for stream i of the group (0: the stream takes no part and is not touched), ids_dev the ids of the
+ * participating streams concatenated in group order (conventions of sm_llm_prefill; a frame token index refers to that stream's own token store; at most 512
+ * participating streams).  Per stream the result is what sm_llm_prefill(stream, its ids, counts_host[i]) leaves -- K / V appended, kv_len advanced, last logits,
+ * pending token by arg-max or the stream's sampling rule -- up to fp32 summation order (same 16-bit rounding points; the products see the rows of all streams).
+ * The rows of all streams form ONE activation matrix per pass (at most 2048 rows, cut in order; a stream cut by a pass boundary continues in the next pass): one
+ * pass over the LLM weights instead of one per stream, and per layer one ragged RoPE + append launch and one sm_llm_attention_ragged launch over a device-side
+ * table uploaded once per call.  kv_fp8 models, head_dim != 128 and H / KV outside {1, 2, 4, 8} run sm_llm_prefill stream by stream instead (same results, no
+ * batching), as does a call with one participating stream.  Refused while the HIP stream is capturing (the table upload synchronises). */
+int sm_group_llm_prefill(sm_stream_group* g, const int32_t* ids_dev, const int32_t* counts_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * f2 ingest front-end, codec half: baseline JPEG (Motion-JPEG AVI frames, stills) -> RGB u8 in HBM (csrc/jpeg.hip).  Replaces the

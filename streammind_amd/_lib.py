@@ -112,6 +112,9 @@ SIGNATURES = {
     "sm_llm_decode_attention_fp8_tab": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "sm_kv_fp8_expand": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "sm_llm_attention_fp8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]),
+    "sm_llm_attention_ragged_plan": (i32, [vp, i32, i32, i32, i32, i32, sz, vp, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "sm_llm_attention_ragged": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, i32, vp, vp]),
+    "sm_rope_kv_append_ragged": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
     "sm_swiglu": (i32, [vp, i32, i32, vp, vp]),
     "sm_argmax": (i32, [vp, i32, vp, vp]),
     "sm_model_create": (i32, [C.POINTER(sm_config_t), C.POINTER(vp)]),
@@ -165,6 +168,7 @@ SIGNATURES = {
     "sm_group_push_frames": (i32, [vp, vp, i32, vp, vp, vp]),
     "sm_group_push_pooled": (i32, [vp, vp, i32, vp, vp, vp]),
     "sm_group_llm_decode": (i32, [vp, C.POINTER(C.c_int32), i32, vp, vp]),
+    "sm_group_llm_prefill": (i32, [vp, vp, C.POINTER(C.c_int32), vp]),
     "sm_jpeg_info": (i32, [vp, sz, C.POINTER(sm_jpeg_info_t)]),
     "sm_jpeg_decode_coefs": (i32, [vp, sz, C.POINTER(sm_jpeg_info_t), vp, vp]),
     "sm_jpeg_planes_bytes": (sz, [C.POINTER(sm_jpeg_info_t), i32]),

@@ -10,8 +10,11 @@
 //   PV MFMA wants in its B operand: no transpose, no LDS round trip, no cross-lane traffic for P.
 //   V is consumed as V^T ([d][keys]); the producers (QKV GEMM epilogue / KV-append kernel) write it that way.
 #include <stdlib.h>
+#include <algorithm>
 #include <atomic>
 #include <type_traits>
+#include <utility>
+#include <vector>
 #include "common.h"
 #include "host.h"
 
@@ -1917,6 +1920,374 @@ extern "C" int sm_llm_attention_fp8(const void* q, const void* kcache, const voi
     }
     if (p.splits > 1) {
         attn_combine_kernel<<<dim3((unsigned)rows, 1), 64, 0, st>>>(p.part_o, p.part_ml, p.splits, (int)rows, dh, p.c, p.ctx, 0, 0, 0);
+        SM_LAUNCH_CHECK();
+    }
+    return SM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ragged causal attention over the 16-bit caches of many streams
+// sm_llm_attention_ragged: the query rows of ONE activation matrix belong to S streams (stream s: rows row0_s .. row0_s + n_s - 1 at positions pos0_s ..), every
+// stream's rows attend to that stream's own cache (K [cap_s][KV * 128], V^T [KV * 128][cap_s], bf16 or fp16; pointers and (row0, n, pos0, cap) in device tables).
+// It is the attention of a batched prefill (sm_group_llm_prefill) and, with S = 1, the short-chunk / long-context kernel of the 16-bit cache: prefill_attn_kernel
+// gives a 16-row chunk 32 blocks that each walk the whole context, four of them over the same K / V.
+//   * tile: 128 rows = the (query, head of the group) pairs of one K / V group of one stream -- chunk_attn_fp8_kernel's row mapping (row r = query r / G, head
+//     kvh * G + r % G, G = H / KV in {1, 2, 4, 8}), so one pass over a 64-key tile serves every head of the group; a wave owns 32 rows (consecutive queries: short
+//     diagonal, softmax inside the wave) and skips key tiles past its last query or in front of its first query's window.
+//   * grid = (work item, K / V group, key split), the group fastest; work items are (stream, query tile) pairs the HOST sorted by visible key range, longest
+//     first.  One `splits` for the launch: every item cuts its own range [window start & ~63, last query + 1) into that many pieces of whole 64-key tiles; a piece
+//     past the end leaves (0, -inf, 0).  Partials lie in attn_combine_kernel's layout with the matrix row as the row; one split writes the 16-bit context.
+//   * K / V^T tiles go global -> LDS by DMA (16 B per lane, double-buffered, 2 x 32 KiB per block: two blocks per CU), the K row permutation and both chunk
+//     swizzles of prefill_attn_kernel on the per-lane SOURCE offset (a scalar tile base that advances + 32-bit lane offsets that do not); fragments are read a
+//     batch ahead of the MFMAs and the arithmetic is that kernel's (scaled log2 domain, P rounded to the operand type before PV and before the row sum, which rides
+//     the matrix pipe).
+//   * dead positions -- keys past the stream's newest row inside its last tile, keys in front of the tile's earliest window start, rows past the stream's end --
+//     may hold any bytes: dead scores are SELECTED to -inf and dead V^T words to 0 (P = 0 times a NaN would be a NaN), dead rows redo the stream's last query and
+//     store nothing.
+struct RaggedP {
+    const bf16_t* q; bf16_t* ctx;               // [rows][H * 128]
+    const void* const* kc; const void* const* vtc;      // [S] cache pointers of this layer
+    const int32_t* seg;                         // [S][4]: row0, n, pos0, cap
+    const int32_t* work;                        // [items][2]: stream, query tile
+    int rows, H, KV, g_shift, window, splits;
+    float* part_o; float* part_ml;              // splits > 1: [split][rows * H][128], [split][rows * H][2]
+    float c;
+};
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void ragged_attn_kernel(RaggedP p) {
+    constexpr int DH = 128, KROW = 256, TILE_BYTES = 32768, DF = 8, KSQ = 4;
+    __shared__ __attribute__((aligned(16))) char lds[2 * TILE_BYTES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g = lane >> 4;
+    const int L = blockIdx.x;
+    const int kvh = L % p.KV, z = (L / p.KV) % p.splits, item = L / (p.KV * p.splits);
+    const int sidx = p.work[2 * item], qtile = p.work[2 * item + 1];
+    const int row0 = p.seg[4 * sidx], n = p.seg[4 * sidx + 1], pos0 = p.seg[4 * sidx + 2], cap = p.seg[4 * sidx + 3];
+    const int gs = p.g_shift, tq0 = qtile * (128 >> gs);                // first query of the tile (of the stream's own rows)
+    const int nk = pos0 + n;
+    bf16x8 qf[2][KSQ];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const int row = wave * 32 + qb * 16 + i;
+        const int qc = min(tq0 + (row >> gs), n - 1);                   // a row past the stream's end redoes its last query and stores nothing
+        const bf16_t* src = p.q + ((size_t)(row0 + qc) * p.H + (kvh << gs) + (row & ((1 << gs) - 1))) * DH + g * 8;
+#pragma unroll
+        for (int ks = 0; ks < KSQ; ++ks) qf[qb][ks] = *(const bf16x8*)(src + ks * 32);
+    }
+    const int wq0 = tq0 + ((wave * 32) >> gs);
+    const bool active = wq0 < n;
+    const int pw_first = pos0 + wq0, pw_last = pos0 + min(tq0 + ((wave * 32 + 31) >> gs), n - 1);      // the wave's first and last query position
+    const int lo_min = p.window > 0 ? max(0, pos0 + tq0 - p.window + 1) : 0;                           // earliest visible key of any query of the tile
+    const int k_end_t = pos0 + min(tq0 + (128 >> gs), n);
+    const int bps = (((k_end_t - (lo_min & ~63) + 63) >> 6) + p.splits - 1) / p.splits;                // 64-key tiles per split
+    const int k_begin = (lo_min & ~63) + z * bps * 64, k_end = min(k_end_t, k_begin + bps * 64);
+
+    f32x4 o[2][DF];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+        for (int df = 0; df < DF; ++df) o[qb][df] = f32x4{0, 0, 0, 0};
+    float m_run[2] = {-INFINITY, -INFINITY};
+    f32x4 lsum[2] = {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}};
+    bf16x8 ones;
+    {
+        const uint32_t one2 = pack16<F16>(1.0f, 1.0f);
+        ones = __builtin_bit_cast(bf16x8, u32x4{one2, one2, one2, one2});
+    }
+    // DMA sources: wave w brings the 1-KiB pieces 4 w .. 4 w + 3 of the K tile (4 permuted key rows of 256 B) and of the V^T tile (8 dims x 64 keys).  A tile never
+    // runs past the cache: cap is a multiple of 64
+    const long k_rs = (long)p.KV * DH * 2;                               // bytes per key row
+    const char* kt = (const char*)p.kc[sidx] + (size_t)kvh * DH * 2 + (long)k_begin * k_rs;
+    const char* vtt = (const char*)p.vtc[sidx] + ((size_t)kvh * DH * cap + k_begin) * 2;
+    uint32_t koff[4], voff[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int P = wave * 4 + j;
+        const int R = P * 4 + (lane >> 4), slot = lane & 15, r5 = R & 31;
+        const int key = (R & 32) | (((r5 >> 2) & 3) << 3) | (((r5 >> 4) & 1) << 2) | (r5 & 3);          // LDS row R holds key inv(R)
+        koff[j] = (uint32_t)(key * (int)k_rs + ((slot ^ (R & 15)) * 16));
+        const int d = P * 8 + (lane >> 3), s8 = lane & 7;
+        voff[j] = (uint32_t)((d * cap + ((s8 ^ (d & 7)) * 8)) * 2);
+    }
+    auto issue = [&](int bufi) {
+        char* Kl = lds + bufi * TILE_BYTES;
+        char* Vl = Kl + 16384;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            __builtin_amdgcn_global_load_lds((gbl_ptr_a)(kt + koff[j]), (lds_ptr_a)(Kl + (wave * 4 + j) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_ptr_a)(vtt + voff[j]), (lds_ptr_a)(Vl + (wave * 4 + j) * 1024), 16, 0, 0);
+        }
+        kt += 64 * k_rs;
+        vtt += 128;
+    };
+    if (k_begin < k_end) issue(0);
+    int buf = 0;
+    for (int kt0 = k_begin; kt0 < k_end; kt0 += 64) {
+        const char* Kl = lds + buf * TILE_BYTES;
+        const char* Vl = Kl + 16384;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                  // every wave's pieces of this tile have landed; everyone is done with the other buffer
+        if (kt0 + 64 < k_end) issue(buf ^ 1);
+        buf ^= 1;
+        // (wave-uniform) nothing of this tile is visible to the wave: past its last query, or in front of its first query's window
+        if (!active || kt0 > pw_last || (p.window > 0 && kt0 + 64 <= pw_first - p.window + 1)) continue;
+        const bool half = kt0 + 32 >= k_end;          // the tile's second 32-key block lies past the last visible key
+        bf16x8 fa[8], fb[8];
+        // ---- batch 1, 2: the K fragments of both key blocks
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int ks = 0; ks < KSQ; ++ks) {
+                const int rho = f * 16 + i;
+                fa[f * 4 + ks] = *(const bf16x8*)(Kl + rho * KROW + (((ks * 4 + g) ^ (rho & 15)) * 16));
+            }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int ks = 0; ks < KSQ; ++ks) {
+                const int rho = 32 + f * 16 + i;
+                fb[f * 4 + ks] = *(const bf16x8*)(Kl + rho * KROW + (((ks * 4 + g) ^ (rho & 15)) * 16));
+            }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 s[2][2][2];
+        // ---- S^T = K . Q^T, key block 0
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+#pragma unroll
+            for (int ks = 0; ks < KSQ; ++ks) {
+                a0 = mfma16<F16>(fa[f * 4 + ks], qf[0][ks], a0);
+                a1 = mfma16<F16>(fa[f * 4 + ks], qf[1][ks], a1);
+            }
+            s[0][0][f] = a0;
+            s[1][0][f] = a1;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- batch 3: the V^T fragments of key block 0 (into the registers QK 0 has just released)
+#pragma unroll
+        for (int df = 0; df < DF; ++df) {
+            const int d = df * 16 + i;
+            fa[df] = *(const bf16x8*)(Vl + d * 128 + ((g ^ (d & 7)) * 16));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (!half) {
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+                f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+#pragma unroll
+                for (int ks = 0; ks < KSQ; ++ks) {
+                    a0 = mfma16<F16>(fb[f * 4 + ks], qf[0][ks], a0);
+                    a1 = mfma16<F16>(fb[f * 4 + ks], qf[1][ks], a1);
+                }
+                s[0][1][f] = a0;
+                s[1][1][f] = a1;
+            }
+        } else {
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+                s[0][1][f] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                s[1][1][f] = s[0][1][f];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- batch 4: the V^T fragments of key block 1
+#pragma unroll
+        for (int df = 0; df < DF; ++df) {
+            const int d = df * 16 + i;
+            fb[df] = *(const bf16x8*)(Vl + d * 128 + (((4 + g) ^ (d & 7)) * 16));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // (block-uniform) only the last tile of the stream's cache and the first of a window hold dead keys: their V^T words (two keys each; fragment word w of
+        // block kb = keys kt0 + 32 kb + 8 g + 2 w, + 1) are selected to zero -- their P is 0, and 0 x NaN is not
+        const bool has_dead = kt0 + 64 > nk || kt0 < lo_min;
+        if (has_dead) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                u32x4 keep;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int k0 = kt0 + kb * 32 + g * 8 + 2 * w;
+                    keep[w] = ((k0 >= nk || k0 < lo_min) ? 0u : 0xffffu) | ((k0 + 1 >= nk || k0 + 1 < lo_min) ? 0u : 0xffff0000u);
+                }
+#pragma unroll
+                for (int df = 0; df < DF; ++df) {
+                    bf16x8& v = kb ? fb[df] : fa[df];
+                    v = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, v) & keep);
+                }
+            }
+        }
+        // ---- mask + online softmax (lane-local query = lane & 15).  (wave-uniform) the selects run only where the tile holds dead keys, reaches past the wave's
+        // first query or starts in front of its last query's window; a dead key's score may be NaN here, it is selected away like the masked ones
+        const bool edge = has_dead || kt0 + 63 > pw_first || (p.window > 0 && kt0 < pw_last - p.window + 1);
+        if (edge) {
+            // (the lane's query positions are worked out here, from a lane id the compiler cannot trace back: as values of the prologue they would sit in registers
+            // through every tile -- the kernel has none to spare)
+            int i2 = i;
+            asm volatile("" : "+v"(i2));
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                const int lim = pos0 + min(tq0 + ((wave * 32 + qb * 16 + i2) >> gs), n - 1);          // last visible key of this lane's query (< nk)
+                const int lo = p.window > 0 ? max(lim - p.window + 1, lo_min) : 0;                    // first visible key
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int f = 0; f < 2; ++f)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int key = kt0 + kb * 32 + g * 8 + f * 4 + r;
+                            s[qb][kb][f][r] = (key > lim || key < lo) ? -INFINITY : s[qb][kb][f][r];
+                        }
+            }
+        }
+        bf16x8 pf[2][2];
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[qb][kb][f][r]);
+            mx = xor32_max(xor16_max(mx));
+            const float m_new = fmaxf(m_run[qb], mx);
+            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;                 // a row that has seen no key yet keeps m = -inf: guard the subtraction
+            const float mc = m_use * p.c;
+            const bool moved = m_new != m_run[qb];
+            const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run[qb], p.c, -mc));
+            m_run[qb] = m_new;
+            const f32x2 c2 = {p.c, p.c}, mc2 = {-mc, -mc};
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                u32x4 pv;
+                if (kb == 1 && half) {
+                    pf[qb][1] = __builtin_bit_cast(bf16x8, u32x4{0, 0, 0, 0});
+                    continue;
+                }
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+#pragma unroll
+                    for (int r = 0; r < 4; r += 2) {
+                        const f32x2 t = f32x2{s[qb][kb][f][r], s[qb][kb][f][r + 1]} * c2 + mc2;
+                        const f32x2 e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+                        pv[f * 2 + (r >> 1)] = pack16<F16>(e[0], e[1]);
+                    }
+                pf[qb][kb] = __builtin_bit_cast(bf16x8, pv);
+            }
+            if (__builtin_amdgcn_ballot_w64(moved) != 0) {
+#pragma unroll
+                for (int df = 0; df < DF; ++df) o[qb][df] *= alpha;
+                lsum[qb] *= alpha;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- O^T += V^T . P^T
+        lsum[0] = mfma16<F16>(ones, pf[0][0], lsum[0]);
+        lsum[1] = mfma16<F16>(ones, pf[1][0], lsum[1]);
+#pragma unroll
+        for (int df = 0; df < DF; ++df) {
+            o[0][df] = mfma16<F16>(fa[df], pf[0][0], o[0][df]);
+            o[1][df] = mfma16<F16>(fa[df], pf[1][0], o[1][df]);
+        }
+        if (!half) {
+            lsum[0] = mfma16<F16>(ones, pf[0][1], lsum[0]);
+            lsum[1] = mfma16<F16>(ones, pf[1][1], lsum[1]);
+#pragma unroll
+            for (int df = 0; df < DF; ++df) {
+                o[0][df] = mfma16<F16>(fb[df], pf[0][1], o[0][df]);
+                o[1][df] = mfma16<F16>(fb[df], pf[1][1], o[1][df]);
+            }
+        }
+    }
+    // ---- store: lane (g, i) holds d = df*16 + g*4 + 0..3 of its two rows; every register of lsum holds the row sum.  (The output rows are worked out again from an
+    // opaque lane id, for the same reason)
+    int lane2 = lane;
+    asm volatile("" : "+v"(lane2));
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const float l = lsum[qb][0];
+        const int row = wave * 32 + qb * 16 + (lane2 & 15), qi = tq0 + (row >> gs);
+        if (qi >= n) continue;
+        const size_t orow = (size_t)(row0 + qi) * p.H + (kvh << gs) + (row & ((1 << gs) - 1));
+        if (p.splits == 1) {
+            const float inv = 1.0f / l;
+            bf16_t* dst = p.ctx + orow * DH + (lane2 >> 4) * 4;
+#pragma unroll
+            for (int df = 0; df < DF; ++df) {
+                const f32x4 v = o[qb][df] * inv;
+                *(u32x2*)(dst + df * 16) = u32x2{pack16<F16>(v[0], v[1]), pack16<F16>(v[2], v[3])};
+            }
+        } else {
+            const size_t prow = (size_t)z * p.rows * p.H + orow;
+            float* dst = p.part_o + prow * DH + (lane2 >> 4) * 4;
+#pragma unroll
+            for (int df = 0; df < DF; ++df) *(f32x4*)(dst + df * 16) = o[qb][df];
+            if (lane2 < 16) *(f32x2*)(p.part_ml + prow * 2) = f32x2{m_run[qb], l};
+        }
+    }
+}
+
+// Host half: checks the per-stream (row0, n, pos0, cap) of a launch, lists its (stream, query tile) work items with the longest visible key range first and picks
+// the launch's key splits -- chunk_fp8_splits' rule with the items of ALL streams in the place of one chunk's query tiles and the longest item's key tiles.
+extern "C" int sm_llm_attention_ragged_plan(const int32_t* seg_host, int S, int rows, int H, int KV, int window, size_t workspace_floats, int32_t* work_host,
+                                            int max_items, int* n_work, int* splits) {
+    SM_REQUIRE(seg_host && work_host && n_work && splits && S > 0 && rows > 0 && window >= 0 && H > 0 && KV > 0 && H % KV == 0, "sm_llm_attention_ragged_plan: bad args");
+    const int G = H / KV;
+    SM_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "sm_llm_attention_ragged_plan: H / KV = %d (1, 2, 4 or 8 query heads per K / V head)", G);
+    const int QT = 128 / G;
+    std::vector<std::pair<int, int>> items;           // (visible keys, index)
+    std::vector<int32_t> raw;
+    int next_row = 0;
+    for (int s = 0; s < S; ++s) {
+        const int row0 = seg_host[4 * s], n = seg_host[4 * s + 1], pos0 = seg_host[4 * s + 2], cap = seg_host[4 * s + 3];
+        SM_REQUIRE(n > 0 && pos0 >= 0 && cap > 0 && cap % 64 == 0 && pos0 + n <= cap, "sm_llm_attention_ragged_plan: stream %d: n = %d, pos0 = %d, cap = %d (n > 0, cap %% 64, pos0 + n <= cap)", s, n, pos0, cap);
+        SM_REQUIRE(row0 >= next_row && row0 + n <= rows, "sm_llm_attention_ragged_plan: stream %d: rows %d .. %d overlap the stream before or pass the matrix (%d rows)", s, row0, row0 + n - 1, rows);
+        next_row = row0 + n;
+        for (int t = 0; t * QT < n; ++t) {
+            const int lo = window > 0 && pos0 + t * QT - window + 1 > 0 ? (pos0 + t * QT - window + 1) & ~63 : 0;
+            const int end = pos0 + (t * QT + QT < n ? t * QT + QT : n);
+            items.push_back({end - lo, (int)raw.size() / 2});
+            raw.push_back(s); raw.push_back(t);
+        }
+    }
+    SM_REQUIRE((int)items.size() <= max_items, "sm_llm_attention_ragged_plan: %d work items exceed the list's %d", (int)items.size(), max_items);
+    std::stable_sort(items.begin(), items.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
+    for (size_t k = 0; k < items.size(); ++k) { work_host[2 * k] = raw[2 * items[k].second]; work_host[2 * k + 1] = raw[2 * items[k].second + 1]; }
+    *n_work = (int)items.size();
+    *splits = workspace_floats ? chunk_fp8_splits((int)items.size(), KV, cdiv(items[0].first, 64), (size_t)rows * H, workspace_floats, 128) : 1;
+    return SM_OK;
+}
+
+extern "C" int sm_llm_attention_ragged(const void* q, const void* const* kc_tab_dev, const void* const* vtc_tab_dev, const int32_t* seg_dev, const int32_t* work_dev,
+                                       int n_work, int rows, int H, int KV, int dh, int window, int f16, float* workspace, size_t workspace_floats, int splits,
+                                       void* ctx, void* stream) {
+    SM_REQUIRE(q && kc_tab_dev && vtc_tab_dev && seg_dev && work_dev && ctx && n_work > 0 && rows > 0 && window >= 0 && H > 0 && KV > 0, "sm_llm_attention_ragged: bad args");
+    SM_REQUIRE(dh == 128, "sm_llm_attention_ragged: head_dim 128 only (got %d)", dh);
+    SM_REQUIRE(H % KV == 0, "sm_llm_attention_ragged: H %% KV (H = %d, KV = %d)", H, KV);
+    const int G = H / KV;
+    SM_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "sm_llm_attention_ragged: H / KV = %d (1, 2, 4 or 8 query heads per K / V head)", G);
+    SM_REQUIRE(splits >= 1 && splits <= 64, "sm_llm_attention_ragged: 1 <= splits <= 64 (got %d)", splits);
+    const size_t prow = (size_t)rows * H;
+    SM_REQUIRE(splits == 1 || (workspace && workspace_floats >= (size_t)splits * prow * (dh + 2)), "sm_llm_attention_ragged: %d splits of %zu rows do not fit a workspace of %zu floats", splits, prow, workspace_floats);
+    SM_REQUIRE((((uintptr_t)q | (uintptr_t)ctx | (uintptr_t)workspace) & 15) == 0, "sm_llm_attention_ragged: q, ctx and the workspace must be 16-byte aligned");
+    SM_REQUIRE((long)n_work * KV * splits < (1L << 31), "sm_llm_attention_ragged: grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    RaggedP p;
+    p.q = (const bf16_t*)q; p.ctx = (bf16_t*)ctx; p.kc = kc_tab_dev; p.vtc = vtc_tab_dev; p.seg = seg_dev; p.work = work_dev;
+    p.rows = rows; p.H = H; p.KV = KV; p.window = window; p.splits = splits;
+    p.g_shift = G == 1 ? 0 : G == 2 ? 1 : G == 4 ? 2 : 3;
+    p.part_o = workspace; p.part_ml = splits > 1 ? workspace + (size_t)splits * prow * dh : nullptr;
+    p.c = (1.0f / sqrtf((float)dh)) * 1.4426950408889634f;
+    {
+        SmProfScope prof(SM_PROF_ATTN, st);
+        const dim3 grid((unsigned)(n_work * KV * splits));
+        if (f16) ragged_attn_kernel<true><<<grid, 256, 0, st>>>(p);
+        else ragged_attn_kernel<false><<<grid, 256, 0, st>>>(p);
+        SM_LAUNCH_CHECK();
+    }
+    if (splits > 1) {
+        // (rows of the matrix that belong to no stream have no partials: the merge leaves unspecified values in their context rows, as the kernel leaves them unwritten)
+        attn_combine_kernel<<<dim3((unsigned)prow, 1), 64, 0, st>>>(p.part_o, p.part_ml, splits, (int)prow, dh, p.c, p.ctx, 0, 0, f16);
         SM_LAUNCH_CHECK();
     }
     return SM_OK;

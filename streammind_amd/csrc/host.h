@@ -71,6 +71,9 @@ int sm_rope_kv_append_ex(const float* qkv, int n, int pos0, int H, int KV, int d
 int sm_embed_splice_ex(const int32_t* ids, int n, const void* table, const float* tokens, int D, float* out, int f16, int vocab,
                        int n_tok, void* stream);
 int sm_swiglu_ex(const float* gu, int M, int F, void* out, int f16, void* stream);
+// vecops.hip: sm_embed_splice_ex for the rows of S streams in one matrix (seg [S][4] = row0, n, pos0, cap on the device; per-stream token stores and their sizes)
+int sm_embed_splice_ragged(const int32_t* ids, int rows, const int32_t* seg, int S, const float* const* tok_tab, const int32_t* ntok, const void* table, int D,
+                           float* out, int f16, int vocab, void* stream);
 // window: Mistral's sliding_window (a query at position p sees keys (p - window, p]); 0 = full causal
 int sm_llm_decode_attention_seg(const void* q_bf16, const SmDecodeSeg& seg, int S, int H, int KV, int dh, int S_max, float* workspace,
                                 int splits_max, void* ctx_bf16, int f16, void* stream, int window = 0);           // attention.hip

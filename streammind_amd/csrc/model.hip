@@ -1395,6 +1395,9 @@ struct sm_stream_group {
     DevBuf d_samp;               // > SM_MAX_SEG streams with a sampled one among them: [S] rules, [S] pending-token words (SmSampleTab), uploaded once per call
     DevBuf d_tab;                // > SM_MAX_SEG streams: [layers][S] K pointers, [layers][S] V^T pointers, [S] start positions (SmDecodeSegTab), uploaded once per call
     bool d_ready = false;
+    // batched prefill scratch, allocated (and grown) by sm_group_llm_prefill: the per-call table, the streams' last rows (fp32 and normalised), their logits, the
+    // key-split partials of the ragged attention
+    DevBuf p_tab, p_last, p_xnb, p_log, p_ws;
 };
 
 extern "C" int sm_group_create(sm_stream** streams, int S, sm_stream_group** out) {
@@ -1911,5 +1914,183 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
     // each stream's own "last logits" as sm_llm_decode would have left them
     for (int t = 0; t < S; ++t)
         SM_HIP(hipMemcpyAsync(act[t]->lmlog.p, g->d_log.as<float>() + (size_t)t * V, (size_t)V * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batched ragged prefill
+// The new ids of every participating stream of a group in ONE activation matrix per pass (at most LLM_CHUNK rows, packed in group order; a stream cut by a pass
+// boundary continues in the next pass at its advanced position): the linears, norms, SwiGLU and the o / down epilogues are llm_layers' calls with n = the pass's
+// rows -- one pass over the weights for all streams, where sm_llm_prefill per stream streams them once each (a chunk of <= 128 rows is bound by exactly that).
+// What is per stream by nature -- embedding + splice, RoPE + append, causal attention against the stream's own cache, the last row's head -- runs as ONE launch
+// over a device-side table that is uploaded once per call: per participating stream the K / V^T pointers of every layer, its token store, and per pass its
+// (row0, n, pos0, cap), the attention's sorted work list and the append's row tiles.  Capacities are not equalised: every stream keeps its own pitch.
+// the last row of every stream that ends in this pass -> its row of the head's input
+__global__ void gather_last_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ seg, const int32_t* __restrict__ fin, int D, float* __restrict__ out) {
+    const int s = blockIdx.x, dst = fin[s];
+    if (dst < 0) return;
+    const float* src = x + (size_t)(seg[4 * s] + seg[4 * s + 1] - 1) * D;
+    for (int c = threadIdx.x; c < D; c += blockDim.x) out[(size_t)dst * D + c] = src[c];
+}
+extern "C" int sm_group_llm_prefill(sm_stream_group* g, const int32_t* ids_dev, const int32_t* counts_host, void* stream) {
+    SM_REQUIRE(g && ids_dev && counts_host && g->m->c.llm_layers > 0, "sm_group_llm_prefill: bad args / perception-only model");
+    sm_model* m = g->m;
+    const sm_config_t& c = m->c;
+    hipStream_t st = (hipStream_t)stream;
+    {   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess) SM_REQUIRE(cs == hipStreamCaptureStatusNone, "sm_group_llm_prefill: the HIP stream is capturing (the call uploads its table and synchronises): run it eagerly");
+        else (void)hipGetLastError(); }
+    std::vector<sm_stream*> act;
+    std::vector<int> cnt;
+    long total = 0;
+    for (size_t i = 0; i < g->streams.size(); ++i) {
+        SM_REQUIRE(counts_host[i] >= 0, "sm_group_llm_prefill: stream %zu: negative count %d", i, counts_host[i]);
+        if (!counts_host[i]) continue;
+        sm_stream* s = g->streams[i];
+        SM_REQUIRE(s->kv_len + counts_host[i] <= s->max_seq, "sm_group_llm_prefill: stream %zu: context %d + %d exceeds max_seq %d", i, s->kv_len, counts_host[i], s->max_seq);
+        act.push_back(s); cnt.push_back(counts_host[i]); total += counts_host[i];
+    }
+    const int P = (int)act.size();
+    SM_REQUIRE(P >= 1, "sm_group_llm_prefill: no stream with new ids");
+    SM_REQUIRE(P <= SM_GROUP_DECODE_MAX, "sm_group_llm_prefill: %d participating streams exceed %d", P, SM_GROUP_DECODE_MAX);
+    const int ld = c.llm_hidden, H = c.llm_heads, KV = c.llm_kv_heads, dh = ld / H, qn = H * dh, kn = KV * dh, V = c.llm_vocab, G = H / KV;
+    int rc;
+    // the fp8 cache (its ragged append and attention do not exist yet), other head shapes, and a lone stream (its own loop, today's numerics): stream by stream
+    if (m->kv_fp8 || dh != 128 || H % KV != 0 || !(G == 1 || G == 2 || G == 4 || G == 8) || P == 1) {
+        size_t off = 0;
+        for (int t = 0; t < P; ++t) { if ((rc = sm_llm_prefill(act[t], ids_dev + off, cnt[t], stream))) return rc; off += cnt[t]; }
+        return SM_OK;
+    }
+    sm_model::LlmWs* W;
+    if ((rc = m->llm_workspace(stream, &W))) return rc;
+    for (int t = 0; t < P; ++t)
+        if ((rc = auto_join(act[t], stream)) || (rc = kv_reserve(act[t], act[t]->kv_len + cnt[t], stream))) return rc;
+    // ---- the table: pointers, then per pass seg / fin / work / tiles (every section 16-byte aligned)
+    const int L = c.llm_layers, CH = sm_model::LLM_CHUNK;
+    static constexpr size_t WS_ROW_SPLITS = 2048;                 // key-split partials: (rows x splits) the workspace holds, of H * (dh + 2) floats each (34 MB at Mistral-7B's heads)
+    const size_t ws_floats = WS_ROW_SPLITS * H * (dh + 2);
+    struct Pass { int a, S, rows, n_work, n_tiles, splits; size_t id_off, seg, fin, work, tiles; };
+    std::vector<Pass> passes;
+    std::vector<char> blob;
+    auto section = [&](size_t bytes) { const size_t o = (blob.size() + 15) & ~(size_t)15; blob.resize(o + bytes); return o; };
+    const size_t o_kc = section((size_t)L * P * sizeof(void*)), o_vtc = section((size_t)L * P * sizeof(void*)), o_tok = section((size_t)P * sizeof(void*)),
+                 o_ntok = section((size_t)P * 4);
+    for (int t = 0; t < P; ++t) {
+        for (int l = 0; l < L; ++l) { ((void**)(blob.data() + o_kc))[(size_t)l * P + t] = act[t]->kc[l].p; ((void**)(blob.data() + o_vtc))[(size_t)l * P + t] = act[t]->vtc[l].p; }
+        ((void**)(blob.data() + o_tok))[t] = act[t]->tokens.p;
+        ((int32_t*)(blob.data() + o_ntok))[t] = act[t]->max_frames;
+    }
+    {
+        int t = 0, done_t = 0;               // next stream and how many of its rows earlier passes took
+        size_t id_off = 0;
+        std::vector<int32_t> seg, fin, work, tiles;
+        while (t < P) {
+            Pass ps; ps.a = t; ps.rows = 0; ps.id_off = id_off;
+            seg.clear(); fin.clear(); tiles.clear();
+            while (t < P && ps.rows < CH) {
+                const int take = cnt[t] - done_t < CH - ps.rows ? cnt[t] - done_t : CH - ps.rows;
+                seg.insert(seg.end(), {ps.rows, take, act[t]->kv_len + done_t, act[t]->cap});
+                for (int r = 0; r < take; r += 64) { tiles.push_back((int)fin.size()); tiles.push_back(r); }
+                ps.rows += take; done_t += take;
+                const bool ends = done_t == cnt[t];
+                fin.push_back(ends ? t : -1);
+                if (!ends) break;             // the pass is full; the stream goes on in the next one
+                ++t; done_t = 0;
+            }
+            ps.S = (int)fin.size(); ps.n_tiles = (int)tiles.size() / 2;
+            work.assign((size_t)2 * (ps.rows + ps.S), 0);      // (a stream of n rows has at most n / (128 / G) + 1 query tiles)
+            if ((rc = sm_llm_attention_ragged_plan(seg.data(), ps.S, ps.rows, H, KV, c.llm_sliding_window, ws_floats, work.data(), ps.rows + ps.S, &ps.n_work, &ps.splits))) return rc;
+            ps.seg = section(seg.size() * 4); memcpy(blob.data() + ps.seg, seg.data(), seg.size() * 4);
+            ps.fin = section(fin.size() * 4); memcpy(blob.data() + ps.fin, fin.data(), fin.size() * 4);
+            ps.work = section((size_t)ps.n_work * 8); memcpy(blob.data() + ps.work, work.data(), (size_t)ps.n_work * 8);
+            ps.tiles = section(tiles.size() * 4); memcpy(blob.data() + ps.tiles, tiles.data(), tiles.size() * 4);
+            id_off += ps.rows;
+            passes.push_back(ps);
+        }
+    }
+    // ---- scratch of the group (grown only here; nothing enqueued may still read an older buffer: synchronise first)
+    {
+        const size_t need_log = (size_t)P * V * 4, need_last = (size_t)P * ld * 4;
+        if (g->p_tab.bytes < blob.size() || g->p_log.bytes < need_log || g->p_last.bytes < need_last || !g->p_ws.p) {
+            SM_HIP(hipStreamSynchronize(st));
+            if (g->p_tab.bytes < blob.size() && (rc = g->p_tab.alloc(blob.size() * 2))) return rc;
+            if (g->p_log.bytes < need_log && (rc = g->p_log.alloc(need_log))) return rc;
+            if (g->p_last.bytes < need_last && ((rc = g->p_last.alloc(need_last)) || (rc = g->p_xnb.alloc((size_t)P * ld * 2)))) return rc;
+            if (!g->p_ws.p && (rc = g->p_ws.alloc(ws_floats * 4))) return rc;
+        }
+    }
+    SM_HIP(hipMemcpyAsync(g->p_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    SM_HIP(hipStreamSynchronize(st));             // the host blob goes out of scope; once per call
+    const char* tb = (const char*)g->p_tab.p;
+    void* const* tab_kc = (void* const*)(tb + o_kc);
+    void* const* tab_vtc = (void* const*)(tb + o_vtc);
+    const int f16 = c.llm_fp16 ? 1 : 0, od = f16 ? SM_OP_F16 : SM_OP_BF16;
+    float* x = W->emb.as<float>();
+    for (const Pass& ps : passes) {
+        const int n = ps.rows;
+        const int32_t* seg = (const int32_t*)(tb + ps.seg);
+        if ((rc = sm_embed_splice_ragged(ids_dev + ps.id_off, n, seg, ps.S, (const float* const*)(tb + o_tok) + ps.a, (const int32_t*)(tb + o_ntok) + ps.a, m->R.embed->buf.p, ld, x,
+                                         f16, V, stream))) return rc;
+        for (int l = 0; l < L; ++l) {             // llm_layers' chunk branch, with the three per-stream stages over the table
+            const sm_model::LayerW& w = m->R.llm[l];
+            if (l == 0 && (rc = sm_norm_ex(x, n, ld, ld, w.ln1_w, nullptr, c.llm_eps, 0, nullptr, W->xnb.p, ld, od, stream))) return rc;
+            {   sm_linear_t a = lin(m, *w.qkv, W->xnb.p, SM_X_BF16, n, ld);
+                a.out_f32 = W->qkvf.as<float>(); a.ldo = qn + 2 * kn;
+                if ((rc = sm_linear(&a, stream))) return rc; }
+            if ((rc = sm_rope_kv_append_ragged(W->qkvf.as<float>(), seg, (const int32_t*)(tb + ps.tiles), ps.n_tiles, H, KV, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p,
+                                               tab_kc + (size_t)l * P + ps.a, tab_vtc + (size_t)l * P + ps.a, f16, stream))) return rc;
+            if ((rc = sm_llm_attention_ragged(W->qb.p, (const void* const*)(tab_kc + (size_t)l * P + ps.a), (const void* const*)(tab_vtc + (size_t)l * P + ps.a), seg,
+                                              (const int32_t*)(tb + ps.work), ps.n_work, n, H, KV, dh, c.llm_sliding_window, f16, g->p_ws.as<float>(), ws_floats, ps.splits, W->ctxb.p, stream))) return rc;
+            {   sm_linear_t a = lin(m, *w.o, W->ctxb.p, SM_X_BF16, n, qn);
+                a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
+                a.post_ln_gamma = w.ln2_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = W->xnb.p; a.post_ln_ldo = ld;
+                if ((rc = linear_post_norm(a, stream))) return rc; }
+            if (n <= (c.weights_fp8 == 2 ? 16 : 32)) {
+                const Slot& gu = *w.gu;
+                sm_linear_t a = lin(m, gu, W->xnb.p, SM_X_BF16, n, ld);
+                a.N = c.llm_mlp;
+                if (gu.fp4) a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * fp4_rg_bytes((ld + 127) / 128);
+                else if (gu.fp8) { a.w2 = (const char*)gu.buf.p + (size_t)(c.llm_mlp / 16) * ((ld / 32 + 1) / 2) * 1024; a.w2_scale = gu.scale.as<float>() + c.llm_mlp; }
+                else a.w2 = gu.buf.as<bf16_t>() + (size_t)(c.llm_mlp / 16) * (ld / 32) * 512;
+                a.out_bf16 = W->actb.p; a.ldo_bf16 = c.llm_mlp;
+                if ((rc = sm_linear(&a, stream))) return rc;
+            } else {
+                sm_linear_t a = lin(m, *w.gu, W->xnb.p, SM_X_BF16, n, ld);
+                a.act = SM_ACT_SWIGLU_DUAL;
+                a.out_bf16 = W->actb.p; a.ldo_bf16 = c.llm_mlp;
+                if ((rc = sm_linear(&a, stream))) return rc;
+            }
+            {   sm_linear_t a = lin(m, *w.down, W->actb.p, SM_X_BF16, n, c.llm_mlp);
+                a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
+                if (l + 1 < L) { a.post_ln_gamma = m->R.llm[l + 1].ln1_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = W->xnb.p; a.post_ln_ldo = ld; }
+                if ((rc = linear_post_norm(a, stream))) return rc; }
+        }
+        gather_last_rows_kernel<<<ps.S, 256, 0, st>>>(x, seg, (const int32_t*)(tb + ps.fin), ld, g->p_last.as<float>());
+        SM_LAUNCH_CHECK();
+    }
+    for (int t = 0; t < P; ++t) act[t]->kv_len += cnt[t];
+    // ---- head: final norm + lm_head over the P last rows, each stream's logits and pending token
+    if ((rc = sm_norm_ex(g->p_last.as<float>(), P, ld, ld, m->R.llm_norm, nullptr, c.llm_eps, 0, nullptr, g->p_xnb.p, ld, od, stream))) return rc;
+    {   sm_linear_t a = lin(m, *m->R.lm_head, g->p_xnb.p, SM_X_BF16, P, ld);
+        a.out_f32 = g->p_log.as<float>(); a.ldo = V;
+        if ((rc = sm_linear(&a, stream))) return rc; }
+    for (int t = 0; t < P; ++t)
+        SM_HIP(hipMemcpyAsync(act[t]->lmlog.p, g->p_log.as<float>() + (size_t)t * V, (size_t)V * 4, hipMemcpyDeviceToDevice, st));
+    bool any_sampled = false;
+    for (sm_stream* s : act) any_sampled = any_sampled || s->sampled();
+    if (any_sampled) {                    // (kv_len has been advanced: it is the index the chosen token will occupy)
+        for (int b0 = 0; b0 < P; b0 += SM_MAX_SEG) {
+            const int bn = P - b0 < SM_MAX_SEG ? P - b0 : SM_MAX_SEG;
+            SmSamplePack pk;
+            for (int t = 0; t < bn; ++t) { pk.r[t] = sm_sample_rule(&act[b0 + t]->samp, act[b0 + t]->kv_len); pk.tok[t] = act[b0 + t]->next_tok.as<int32_t>(); }
+            if ((rc = sm_sample_rows_seg(g->p_log.as<float>() + (size_t)b0 * V, bn, V, V, pk, stream))) return rc;
+        }
+    } else {
+        for (int b0 = 0; b0 < P; b0 += SM_BIG_SEG) {
+            const int bn = P - b0 < SM_BIG_SEG ? P - b0 : SM_BIG_SEG;
+            SmTokPtrsBig tok;
+            for (int t = 0; t < bn; ++t) tok.p[t] = act[b0 + t]->next_tok.as<int32_t>();
+            if ((rc = sm_argmax_rows_seg_big(g->p_log.as<float>() + (size_t)b0 * V, bn, V, V, tok, stream))) return rc;
+        }
+    }
     return SM_OK;
 }

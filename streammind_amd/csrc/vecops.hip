@@ -831,6 +831,96 @@ extern "C" int sm_rope_kv_append(const float* qkv, int n, int pos0, int H, int K
     return sm_rope_kv_append_ex(qkv, n, pos0, H, KV, dh, cos_tab, sin_tab, q, kcache, vtcache, S_max, 0, stream);
 }
 
+// ---- the rows of S streams in one matrix (sm_group_llm_prefill): seg [S][4] = (row0, n, pos0, cap) per stream, ascending in row0
+// embedding gather + splice: a row's stream is found by bisection over row0; a frame token index refers to THAT stream's token store
+__global__ void embed_splice_ragged_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ seg, int S, const float* const* __restrict__ tok_tab,
+                                           const int32_t* __restrict__ ntok, const bf16_t* __restrict__ table, int D, float* __restrict__ out, int f16, int vocab) {
+    const int row = blockIdx.x;
+    int lo = 0, hi = S - 1;
+    while (lo < hi) {                              // the last stream whose row0 <= row
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[4 * mid] <= row) lo = mid; else hi = mid - 1;
+    }
+    const int id = ids[row];
+    const bool text = id >= 0;
+    const bool ok = text ? id < vocab : -id - 1 < ntok[lo];
+    const float* tokens = tok_tab[lo];
+    for (int c = threadIdx.x; c < D; c += blockDim.x) {
+        float v = 0.f;
+        if (ok) v = text ? (f16 ? h2f(table[(size_t)id * D + c]) : bf2f(table[(size_t)id * D + c])) : tokens[(size_t)(-id - 1) * D + c];
+        out[(size_t)row * D + c] = v;
+    }
+}
+int sm_embed_splice_ragged(const int32_t* ids, int rows, const int32_t* seg, int S, const float* const* tok_tab, const int32_t* ntok, const void* table, int D,
+                           float* out, int f16, int vocab, void* stream) {
+    SM_REQUIRE(ids && seg && tok_tab && ntok && table && out && rows > 0 && S > 0, "sm_embed_splice_ragged: bad args");
+    embed_splice_ragged_kernel<<<rows, 256, 0, (hipStream_t)stream>>>(ids, seg, S, tok_tab, ntok, (const bf16_t*)table, D, out, f16, vocab);
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+// RoPE + append, head_dim 128: one 256-thread block per (64-row tile of ONE stream's rows, head slot).  q / k heads run rope_kv_tile_kernel's operation sequence
+// (16-byte loads, a c - b s / b c + a s in fp32, one rounding) and v heads its LDS transpose, each row at its stream's position into its stream's caches (pitch =
+// that stream's cap) -- also for streams of fewer than 32 rows, where sm_rope_kv_append takes the row kernel: the two forms write the same bytes (tested).
+__global__ __launch_bounds__(256) void rope_kv_ragged_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ seg, const int32_t* __restrict__ tiles,
+                                                             int H, int KV, const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                             bf16_t* __restrict__ q, void* const* __restrict__ kc_tab, void* const* __restrict__ vtc_tab, int f16) {
+    constexpr int DH = 128, HALF = 64;
+    __shared__ bf16_t tile[DH][64 + 2];
+    const int sidx = tiles[2 * blockIdx.x], t0 = tiles[2 * blockIdx.x + 1], hd = blockIdx.y, tid = threadIdx.x;
+    const int row0 = seg[4 * sidx], n = seg[4 * sidx + 1], pos0 = seg[4 * sidx + 2], S_max = seg[4 * sidx + 3];
+    const int tl = tid >> 2, part = tid & 3, t = t0 + tl;
+    const int ld = (H + 2 * KV) * DH;
+    if (hd < H + KV) {
+        if (t >= n) return;
+        const int pos = pos0 + t;
+        const float* x = qkv + (size_t)(row0 + t) * ld + (size_t)hd * DH + part * 16;
+        const float* cp = cos_tab + (size_t)pos * HALF + part * 16;
+        const float* sp = sin_tab + (size_t)pos * HALF + part * 16;
+        bf16_t* dst = (hd < H ? q + ((size_t)(row0 + t) * H + hd) * DH : (bf16_t*)kc_tab[sidx] + ((size_t)pos * KV + (hd - H)) * DH) + part * 16;
+        uint32_t o0[8], o1[8];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const f32x4 a = *(const f32x4*)(x + v * 4), b = *(const f32x4*)(x + HALF + v * 4);
+            const f32x4 c = *(const f32x4*)(cp + v * 4), s_ = *(const f32x4*)(sp + v * 4);
+            float r0[4], r1[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { r0[e] = a[e] * c[e] - b[e] * s_[e]; r1[e] = b[e] * c[e] + a[e] * s_[e]; }
+            o0[v * 2] = pack16_rt(r0[0], r0[1], f16); o0[v * 2 + 1] = pack16_rt(r0[2], r0[3], f16);
+            o1[v * 2] = pack16_rt(r1[0], r1[1], f16); o1[v * 2 + 1] = pack16_rt(r1[2], r1[3], f16);
+        }
+        *(u32x4*)(dst) = u32x4{o0[0], o0[1], o0[2], o0[3]};
+        *(u32x4*)(dst + 8) = u32x4{o0[4], o0[5], o0[6], o0[7]};
+        *(u32x4*)(dst + HALF) = u32x4{o1[0], o1[1], o1[2], o1[3]};
+        *(u32x4*)(dst + HALF + 8) = u32x4{o1[4], o1[5], o1[6], o1[7]};
+        return;
+    }
+    const int kh = hd - H - KV;
+    if (t < n) {
+        const float* x = qkv + (size_t)(row0 + t) * ld + (size_t)hd * DH + part * 32;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+            const f32x4 a = *(const f32x4*)(x + v * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) tile[part * 32 + v * 4 + e][tl] = (bf16_t)cvt16_rt(a[e], f16);
+        }
+    }
+    __syncthreads();
+    const int lane = tid & 63, w = tid >> 6;
+    if (t0 + lane < n) {
+        bf16_t* dstv = (bf16_t*)vtc_tab[sidx] + ((size_t)kh * DH + w * 32) * S_max + pos0 + t0 + lane;
+#pragma unroll 8
+        for (int e = 0; e < 32; ++e) dstv[(size_t)e * S_max] = tile[w * 32 + e][lane];
+    }
+}
+extern "C" int sm_rope_kv_append_ragged(const float* qkv, const int32_t* seg_dev, const int32_t* tiles_dev, int n_tiles, int H, int KV, const float* cos_tab,
+                                        const float* sin_tab, void* q, void* const* kc_tab_dev, void* const* vtc_tab_dev, int f16, void* stream) {
+    SM_REQUIRE(qkv && seg_dev && tiles_dev && cos_tab && sin_tab && q && kc_tab_dev && vtc_tab_dev && n_tiles > 0 && H > 0 && KV > 0, "sm_rope_kv_append_ragged: bad args");
+    SM_REQUIRE((((uintptr_t)qkv | (uintptr_t)q | (uintptr_t)cos_tab | (uintptr_t)sin_tab) & 15) == 0, "sm_rope_kv_append_ragged: qkv, q and the RoPE tables must be 16-byte aligned");
+    rope_kv_ragged_kernel<<<dim3(n_tiles, H + 2 * KV), 256, 0, (hipStream_t)stream>>>(qkv, seg_dev, tiles_dev, H, KV, cos_tab, sin_tab, (bf16_t*)q, kc_tab_dev, vtc_tab_dev, f16);
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+
 // the same for S streams x one token each: row t = stream t at ITS position, appended to ITS caches
 template <class SEG>
 __global__ __launch_bounds__(64) void rope_kv_seg_kernel(const float* __restrict__ qkv, int H, int KV, int dh,

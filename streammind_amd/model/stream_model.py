@@ -352,6 +352,14 @@ class Videollama2MistralForCausalLM:
 
     def _begin_generate(self, seq: List[int], max_new_tokens: int) -> int:
         """prefill `seq` behind the longest cached prefix (KV prefix reuse); returns the number of new tokens that still fit"""
+        max_new_tokens, lcp, ids = self._plan_generate(seq, max_new_tokens)
+        self.stream.set_kv_len(lcp)
+        self.stream.prefill(ids)
+        return max_new_tokens
+
+    def _plan_generate(self, seq: List[int], max_new_tokens: int) -> Tuple[int, int, torch.Tensor]:
+        """the host half of _begin_generate: -> (new tokens that still fit, length of the cached prefix to keep, the ids to prefill behind it); the caller cuts
+        the cache back and prefills -- alone, or with other streams in one NativeStreamGroup.prefill"""
         self._check_ids(seq)
         if len(seq) + max_new_tokens > self.max_seq:
             max_new_tokens = self.max_seq - len(seq)
@@ -363,10 +371,8 @@ class Videollama2MistralForCausalLM:
                 break
             lcp += 1
         lcp = min(lcp, len(seq) - 1, self.stream.kv_len)
-        self.stream.set_kv_len(lcp)
-        self.stream.prefill(torch.tensor(seq[lcp:], dtype=torch.int32, device=self.device))
         self._kv_ids = list(seq)
-        return max_new_tokens
+        return max_new_tokens, lcp, torch.tensor(seq[lcp:], dtype=torch.int32, device=self.device)
 
     def _accept_tokens(self, out: List[int], ids: Sequence[int], seq_len: int, stopping_criteria=None) -> Tuple[List[int], bool]:
         """take the freshly decoded `ids` one by one up to the first stop (EOS / stopping criteria): the accepted ones join

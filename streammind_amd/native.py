@@ -396,6 +396,17 @@ class NativeStreamGroup:
         check(self.lib.sm_group_llm_decode(self.h, mask, n_steps, out.data_ptr(), _stream()), "sm_group_llm_decode")
         return out
 
+    def prefill(self, ids_per_stream: Sequence[Optional[torch.Tensor]]) -> None:
+        """batched ragged prefill (sm_group_llm_prefill): one entry per stream of the group, int32 [n_i] on the GPU (conventions of NativeStream.prefill) or None /
+        empty for a stream that takes no part; per stream the result of its own prefill, with one pass over the LLM weights for all of them"""
+        S = len(self.streams)
+        assert len(ids_per_stream) == S, "one entry (ids or None) per stream of the group"
+        parts = [t for t in ids_per_stream if t is not None and t.numel() > 0]
+        assert parts and all(t.dtype == torch.int32 and t.is_cuda and t.dim() == 1 for t in parts)
+        counts = (C.c_int32 * S)(*[0 if t is None else int(t.numel()) for t in ids_per_stream])
+        ids = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
+        check(self.lib.sm_group_llm_prefill(self.h, ids.data_ptr(), counts, _stream()), "sm_group_llm_prefill")
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.lib.sm_group_destroy(self.h)

@@ -290,7 +290,7 @@ class MultiStreamSession:
     Videollama2MistralForCausalLM per stream, all built on the SAME NativeModel."""
 
     def __init__(self, models, tokenizer, max_new_tokens: int = 1024, decode_chunk: int = 16, continuous: bool = False,
-                 sampling: Optional[Sequence[Optional[dict]]] = None):
+                 sampling: Optional[Sequence[Optional[dict]]] = None, batched_prefill: bool = False):
         """continuous=False: a tick returns when the replies it started are complete (every stream waits for them: the lock-step form).
         continuous=True: replies stay IN FLIGHT across ticks -- a tick is one perception pass for every stream plus `decode_chunk` decode steps of all
         the streams that are replying at that moment, whichever tick started them (one weight pass per step for all of them: a reply of 256 tokens no
@@ -299,7 +299,10 @@ class MultiStreamSession:
         replies (the gate reads the connector state only), so per stream the events are those of the lock-step form -- they are handed out by the tick
         in which they complete; `flush()` finishes what is in flight.
         sampling: per stream None (greedy) or dict(temperature=, top_p=, top_k=, seed=) -- that stream's replies are SAMPLED on the GPU
-        (NativeStream.set_sampling) and still decode through the batched call, next to the greedy streams of the group."""
+        (NativeStream.set_sampling) and still decode through the batched call, next to the greedy streams of the group.
+        batched_prefill=True: the streams that fire in one tick prefill their grown prompts TOGETHER (NativeStreamGroup.prefill, sm_group_llm_prefill: one pass
+        over the LLM weights and one ragged attention launch per layer for all of them) instead of one prefill each; same events, the reply ids are the ids of
+        the same logits up to fp32 summation order.  A fire that waited behind a running reply (continuous mode) still starts with its own prefill."""
         assert len(models) >= 1 and all(m.native is models[0].native for m in models), "the streams must share one NativeModel"
         self.models, self.tok = list(models), tokenizer
         self.native = models[0].native
@@ -307,7 +310,7 @@ class MultiStreamSession:
         self.max_new, self.chunk = max_new_tokens, decode_chunk
         self.prompts: List[Optional[str]] = [None] * len(models)
         self.stats = StreamStats()
-        self.continuous = continuous
+        self.continuous, self.batched_prefill = continuous, batched_prefill
         self.sampling = list(sampling) if sampling is not None else [None] * len(models)
         assert len(self.sampling) == len(models), "one sampling entry (or None) per stream"
         self._replying = {}                                # stream index -> state of the reply in flight
@@ -330,6 +333,7 @@ class MultiStreamSession:
         self.stats.frames += S
         fired = [i for i, d in enumerate(dec_host) if d == 1]
         self.stats.fires += len(fired)
+        self._prefill_q = [None] * S if self.batched_prefill else None         # batched_prefill: the ids of the replies this tick starts, prefilled together below
         if self.continuous:
             for i in fired:
                 upto = self.models[i].stream.num_frames
@@ -337,12 +341,14 @@ class MultiStreamSession:
                     self._pending[i].append(upto)            # behind the running reply (its text belongs to this one's prompt)
                 else:
                     self._start_reply(i, upto)
+            self._prefill_started()
             return self._decode_round(self.chunk)
         if not fired:
             return []
         # ---- every fired stream: its own splice + prefill (prompt growth and KV prefix reuse as in the single-stream loop)
         for i in fired:
             self._start_reply(i, self.models[i].stream.num_frames)
+        self._prefill_started()
         # ---- all of them decode together, to the end
         events = []
         while self._replying:
@@ -359,8 +365,18 @@ class MultiStreamSession:
         seq = m._expand(input_ids[0].tolist())
         if self.sampling[i]:                                # before the prefill: its pending token is the reply's first sampled id
             m.stream.set_sampling(**self.sampling[i])
-        budget = m._begin_generate(seq, self.max_new)
+        if getattr(self, "_prefill_q", None) is not None:      # batched_prefill, inside a tick: the host half now, the prefill with the other fired streams
+            budget, lcp, self._prefill_q[i] = m._plan_generate(seq, self.max_new)
+            m.stream.set_kv_len(lcp)
+        else:
+            budget = m._begin_generate(seq, self.max_new)
         self._replying[i] = {"seq_len": len(seq), "budget": budget, "out": [], "crit": [KeywordsStoppingCriteria(["</s>"], self.tok, input_ids)], "upto": upto}
+
+    def _prefill_started(self) -> None:
+        """batched_prefill: ONE group prefill for the replies this tick started"""
+        q, self._prefill_q = self._prefill_q, None
+        if q is not None and any(t is not None for t in q):
+            self.group.prefill(q)
 
     def _decode_round(self, steps: int) -> List[Tuple[int, StreamEvent]]:
         """up to `steps` decode steps of every reply in flight (one sm_group_llm_decode call: one weight pass per step for all of them); the replies
