@@ -338,6 +338,19 @@ int sm_llm_attention_ragged(const void* q, const void* const* kc_tab_dev, const 
  * sm_rope_kv_append per stream. */
 int sm_rope_kv_append_ragged(const float* qkv, const int32_t* seg_dev, const int32_t* tiles_dev, int n_tiles, int H, int KV, const float* cos_tab,
                              const float* sin_tab, void* q, void* const* kc_tab_dev, void* const* vtc_tab_dev, int f16, void* stream);
+/* the two ragged operators over FP8 (e4m3) K / V caches (format: the FP8 section above; bf16 q / ctx, head_dim 128): stream s's two buffers are kc_tab_dev[s] /
+ * vtc_tab_dev[s] with ITS capacity cap_s from seg_dev -- V^T pitch cap_s, scales at byte offset cap_s * KV * 128 of each buffer.
+ * sm_llm_attention_ragged_fp8: sm_llm_attention_ragged's arguments without f16, same seg / work / splits (sm_llm_attention_ragged_plan serves both), same
+ * workspace rule; the arithmetic is sm_llm_attention_fp8's (with S = 1 and one split: its bits).  Cache positions >= pos0_s + n_s and, with a window,
+ * < pos0_s - window + 1 may hold any bytes, NaN codes and NaN scales included.  SM_EINVAL: dh != 128, H / KV outside {1, 2, 4, 8}, splits outside 1 .. 64, a
+ * workspace too small for splits, misaligned q / ctx / workspace. */
+int sm_llm_attention_ragged_fp8(const void* q_bf16, const void* const* kc_tab_dev, const void* const* vtc_tab_dev, const int32_t* seg_dev, const int32_t* work_dev,
+                                int n_work, int rows, int H, int KV, int dh, int window, float* workspace, size_t workspace_floats, int splits, void* ctx_bf16,
+                                void* stream);
+/* sm_rope_kv_append_fp8 for the rows of S streams in one launch (seg_dev / tiles_dev as sm_rope_kv_append_ragged takes them): q, codes and scales are the bytes
+ * of sm_rope_kv_append_fp8 per stream; nothing outside a stream's positions [pos0_s, pos0_s + n_s) is written. */
+int sm_rope_kv_append_fp8_ragged(const float* qkv, const int32_t* seg_dev, const int32_t* tiles_dev, int n_tiles, int H, int KV, const float* cos_tab,
+                                 const float* sin_tab, void* q_bf16, void* const* kc_tab_dev, void* const* vtc_tab_dev, void* stream);
 /* out[m] = bf16( silu(gu[m][0:F]) * gu[m][F:2F] ) */
 int sm_swiglu(const float* gu, int M, int F, void* out_bf16, void* stream);
 /* greedy argmax over fp32 logits[V] -> token (int32, device) ; first max wins (torch.argmax)           */
@@ -605,8 +618,9 @@ int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_host, int n_st
  * pending token by arg-max or the stream's sampling rule -- up to fp32 summation order (same 16-bit rounding points; the products see the rows of all streams).
  * The rows of all streams form ONE activation matrix per pass (at most 2048 rows, cut in order; a stream cut by a pass boundary continues in the next pass): one
  * pass over the LLM weights instead of one per stream, and per layer one ragged RoPE + append launch and one sm_llm_attention_ragged launch over a device-side
- * table uploaded once per call.  kv_fp8 models, head_dim != 128 and H / KV outside {1, 2, 4, 8} run sm_llm_prefill stream by stream instead (same results, no
- * batching), as does a call with one participating stream.  Refused while the HIP stream is capturing (the table upload synchronises). */
+ * table uploaded once per call -- for kv_fp8 models with sm_model_set_kv_fp8_chunk the FP8 pair, sm_rope_kv_append_fp8_ragged and
+ * sm_llm_attention_ragged_fp8, over the same table.  kv_fp8 models WITHOUT kv_fp8_chunk (multi-row calls read a bf16 expansion there), head_dim != 128 and
+ * H / KV outside {1, 2, 4, 8} run sm_llm_prefill stream by stream instead (same results, no batching), as does a call with one participating stream.  Refused while the HIP stream is capturing (the table upload synchronises). */
 int sm_group_llm_prefill(sm_stream_group* g, const int32_t* ids_dev, const int32_t* counts_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -115,6 +115,8 @@ SIGNATURES = {
     "sm_llm_attention_ragged_plan": (i32, [vp, i32, i32, i32, i32, i32, sz, vp, i32, C.POINTER(i32), C.POINTER(i32)]),
     "sm_llm_attention_ragged": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, i32, vp, vp]),
     "sm_rope_kv_append_ragged": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    "sm_llm_attention_ragged_fp8": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, i32, vp, vp]),
+    "sm_rope_kv_append_fp8_ragged": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "sm_swiglu": (i32, [vp, i32, i32, vp, vp]),
     "sm_argmax": (i32, [vp, i32, vp, vp]),
     "sm_model_create": (i32, [C.POINTER(sm_config_t), C.POINTER(vp)]),

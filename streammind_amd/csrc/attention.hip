@@ -2292,3 +2292,288 @@ extern "C" int sm_llm_attention_ragged(const void* q, const void* const* kc_tab_
     }
     return SM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ ragged causal attention over the FP8 caches of many streams
+// sm_llm_attention_ragged_fp8: ragged_attn_kernel's work decomposition over chunk_attn_fp8_kernel's data path -- the attention of a batched prefill of kv_fp8 +
+// kv_fp8_chunk models.  Grid, work list, seg, splits and the partials' layout are the 16-bit ragged kernel's (one plan serves both); tile (128 (query, head)
+// rows of one K / V group of one stream, a wave = 32 rows, softmax inside the wave, wave-uniform skip of key tiles past the wave's last query or in front of
+// its first query's window), LDS image (8 KiB of K codes with the decode kernel's row permutation, 8 KiB of V^T codes, both chunk-swizzled on the per-lane DMA
+// SOURCE offset, a 512-byte strip of the tile's 64 + 64 scales) and every arithmetic step are the chunk kernel's: codes -> bf16 in registers between ds_read
+// and MFMA, the K scale on the fp32 score, P' = bf16(e * vscale[key]), the row sum over the unscaled rounded e.  Chunk, decode and ragged attention see the
+// same dequantised values; with S = 1 and one split this kernel walks the chunk kernel's tiles in the chunk kernel's order: the same bits (tested).
+// What that kernel takes from S_max is per BLOCK here, from the stream's cap: the start of the scales (cap * KV * 128 into each buffer, K scales [cap][KV],
+// V scales [KV][cap]) and the V^T pitch inside the lane offsets of the DMA.
+// The code tiles are double-buffered as there (2 x 16.5 KiB).  A three-buffer ring with two tiles in flight (49.5 KiB, still two blocks per CU; per-wave
+// vmcnt(5 | 4) in front of a bare s_barrier, the q loads pinned complete in front of the loop) was built and measured against this form in one process: it
+// LOST at every bench shape (group prefill 8 / 32 streams x 32 ids @ 2048: 8.037 / 18.688 against 8.026 / 18.603 ms; one layer's attention 16 @ 4080 and
+// 64 @ 4032: 19.66 / 27.01 against 19.48 / 26.79 us; spread of a leg <= 0.02 ms / 0.1 us) and was taken out again -- DESIGN.md has the runs.
+// Dead data -- keys behind the stream's newest row inside its last tile, keys in front of the tile's earliest window start, q rows of no stream -- may hold any
+// bytes, NaN codes 0x7F and NaN scales included: dead scores are SELECTED to -inf, dead scales and V codes to 0, dead rows redo the stream's last query and
+// store nothing.
+// Kernel resources (compiler's kernel-resource-usage report, -O3, gfx950): 256 VGPRs, 0 AGPRs, 106 SGPRs with 29 SGPR spills (into VGPR lanes), no VGPR spill,
+// ScratchSize 0, 33792 bytes of LDS, occupancy 2 waves / SIMD = two blocks per CU (chunk_attn_fp8_kernel in the same build: 256 VGPRs, 106 SGPRs with 24 SGPR
+// spills, ScratchSize 0, 33792 bytes).
+__global__ __launch_bounds__(256, 2) void ragged_attn_fp8_kernel(RaggedP p) {
+    constexpr int DH = 128, KT = 8192, BUF = 2 * KT + 512;
+    __shared__ __attribute__((aligned(16))) char lds[2 * BUF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g = lane >> 4;
+    const int L = blockIdx.x;
+    const int kvh = L % p.KV, z = (L / p.KV) % p.splits, item = L / (p.KV * p.splits);
+    const int sidx = p.work[2 * item], qtile = p.work[2 * item + 1];
+    const int row0 = p.seg[4 * sidx], n = p.seg[4 * sidx + 1], pos0 = p.seg[4 * sidx + 2], cap = p.seg[4 * sidx + 3];
+    const int gs = p.g_shift, tq0 = qtile * (128 >> gs);                // first query of the tile (of the stream's own rows)
+    const int nk = pos0 + n;
+    const int wq0 = tq0 + ((wave * 32) >> gs);
+    const bool active = wq0 < n;
+    const int pw_first = pos0 + wq0, pw_last = pos0 + min(tq0 + ((wave * 32 + 31) >> gs), n - 1);      // the wave's first and last query position
+    // the item's key range and this block's piece of it
+    const int lo_min = p.window > 0 ? max(0, pos0 + tq0 - p.window + 1) : 0;                           // earliest visible key of any query of the tile
+    const int k_end_t = pos0 + min(tq0 + (128 >> gs), n);
+    const int bps = (((k_end_t - (lo_min & ~63) + 63) >> 6) + p.splits - 1) / p.splits;                // 64-key tiles per split
+    const int k_begin = (lo_min & ~63) + z * bps * 64, k_end = min(k_end_t, k_begin + bps * 64);
+    const int ntile = k_begin < k_end ? (k_end - k_begin + 63) >> 6 : 0;                               // (a piece past the range: none, the block stores (0, -inf, 0))
+
+    f32x4 o[2][8];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+        for (int df = 0; df < 8; ++df) o[qb][df] = f32x4{0, 0, 0, 0};
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+
+    // DMA sources = a scalar tile base that advances + a 32-bit per-lane offset that does not: wave w brings the 1-KiB pieces 2 w, 2 w + 1 of the K tile (8 permuted
+    // key rows each) and of the V^T tile (16 dims x 64 keys each); waves 0 / 1 the tile's K / V scales (lane L: key L).  A tile never runs past the stream's
+    // buffers: cap is a multiple of 64 and k_end <= pos0 + n <= cap
+    const long k_rs = (long)p.KV * DH;
+    const size_t codes = (size_t)cap * p.KV * DH;
+    const uint8_t* kbase = (const uint8_t*)p.kc[sidx];
+    const uint8_t* vbase = (const uint8_t*)p.vtc[sidx];
+    const uint8_t* kt = kbase + kvh * DH + (long)k_begin * k_rs;
+    const uint8_t* vtt = vbase + (size_t)kvh * DH * cap + k_begin;
+    const float* sct = wave == 0 ? (const float*)(kbase + codes) + (size_t)k_begin * p.KV + kvh : (const float*)(vbase + codes) + (size_t)kvh * cap + k_begin;
+    const int sadv = wave == 0 ? 64 * p.KV : 64;
+    const uint32_t soff = lane * (wave == 0 ? p.KV : 1);
+    uint32_t koff[2], voff[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int P = wave * 2 + j;
+        const int R = P * 8 + (lane >> 3), a = R >> 4, x = R & 15;
+        koff[j] = (uint32_t)(((x >> 2) * 16 + a * 4 + (x & 3)) * (int)k_rs + (((lane & 7) ^ ((R >> 1) & 7)) * 16));
+        const int d = P * 16 + (lane >> 2);
+        voff[j] = (uint32_t)(d * cap + (((lane & 3) ^ ((d >> 2) & 3)) * 16));
+    }
+    int ib = 0;                                   // the buffer the next DMA fills
+    auto issue = [&]() {
+        char* Kl = lds + ib * BUF;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            __builtin_amdgcn_global_load_lds((gbl_ptr_a)(kt + koff[j]), (lds_ptr_a)(Kl + (wave * 2 + j) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_ptr_a)(vtt + voff[j]), (lds_ptr_a)(Kl + KT + (wave * 2 + j) * 1024), 16, 0, 0);
+        }
+        if (wave < 2) __builtin_amdgcn_global_load_lds((gbl_ptr_a)(sct + soff), (lds_ptr_a)(Kl + 2 * KT + wave * 256), 4, 0, 0);
+        kt += 64 * k_rs;
+        vtt += 64;
+        sct += sadv;
+        ib ^= 1;
+    };
+    if (ntile > 0) issue();
+    // this lane's two queries (a row past the stream's end redoes its last query and stores nothing), loaded BEHIND the first tile's DMAs (a short item's life is
+    // mostly that first latency) and pinned complete in front of the loop.  The loop counts tiles.  In this form the compiler keeps the loop's scalars in 71
+    // SGPRs; written as the chunk kernel's loop (kt0 from k_begin in steps of 64, q loads not pinned) it spilled 29 of them into VGPR lanes and one layer's
+    // attention took 19.80 / 27.08 us where sm_llm_attention_fp8 took 19.38 / 26.51 (16 @ 4080, 64 @ 4032) -- this form: equal to it, see DESIGN.md
+    int qpos[2];
+    bf16x8 qf[2][4];                                                    // k-step kk*2 + hf: dims kk*64 + g*16 + hf*8 .. +7 (the order the K chunks are consumed in)
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const int row = wave * 32 + qb * 16 + i;
+        const int qc = min(tq0 + (row >> gs), n - 1);
+        qpos[qb] = pos0 + qc;
+        const bf16_t* src = p.q + ((size_t)(row0 + qc) * p.H + (kvh << gs) + (row & ((1 << gs) - 1))) * DH + g * 16;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qf[qb][s] = *(const bf16x8*)(src + (s >> 1) * 64 + (s & 1) * 8);
+    }
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[qb][s]));
+    int buf = 0;
+    for (int t = 0; t < ntile; ++t) {
+        const int kt0 = k_begin + t * 64;
+        const char* Kl = lds + buf * BUF;
+        const char* Vl = Kl + KT;
+        const char* Sl = Vl + KT;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                  // every wave's pieces of this tile have landed; everyone is done with the other buffer
+        if (t + 1 < ntile) issue();
+        buf ^= 1;
+        // (wave-uniform) nothing of this tile is visible to the wave: past its last query, or in front of its first query's window
+        if (!active || kt0 > pw_last || (p.window > 0 && kt0 + 64 <= pw_first - p.window + 1)) continue;
+        // ---- S^T = K . Q^T: fragment a of lane (i, g) = keys kt0 + g*16 + a*4 + 0..3
+        u32x4 kq[4][2];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int rho = a * 16 + i;
+                kq[a][kk] = *(const u32x4*)(Kl + rho * 128 + (((kk * 4 + g) ^ ((rho >> 1) & 7)) * 16));
+            }
+        float s[2][16];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    const bf16x8 kf = kv8_to_bf16(kq[a][kk][hf * 2], kq[a][kk][hf * 2 + 1]);
+                    a0 = mfma16<false>(kf, qf[0][kk * 2 + hf], a0);
+                    a1 = mfma16<false>(kf, qf[1][kk * 2 + hf], a1);
+                }
+            const f32x4 kv = *(const f32x4*)(Sl + (g * 16 + a * 4) * 4);       // the K scales of these four keys multiply the fp32 scores
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { s[0][a * 4 + r] = a0[r] * kv[r]; s[1][a * 4 + r] = a1[r] * kv[r]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);        // (the K fragments are dead before the V fragments take their registers)
+        // ---- the V^T fragments (keys g*16 .. +15 of dim df*16 + i) and the V scales of this lane's sixteen keys
+        u32x4 vq[8];
+#pragma unroll
+        for (int df = 0; df < 8; ++df) {
+            const int d = df * 16 + i;
+            vq[df] = *(const u32x4*)(Vl + d * 64 + ((g ^ ((d >> 2) & 3)) * 16));
+        }
+        const int kb = kt0 + g * 16;                                    // this lane's sixteen keys: kb + j
+        const bool has_dead = kt0 + 64 > nk || kt0 < lo_min;            // (block-uniform) only the last tile of the stream's cache and the first of a window
+        if (has_dead) {
+            uint32_t keep[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const bool dead = kb + j >= nk || kb + j < lo_min;
+                keep[j >> 2] |= dead ? 0u : (0xffu << (8 * (j & 3)));
+            }
+#pragma unroll
+            for (int df = 0; df < 8; ++df)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) vq[df][w] &= keep[w];
+        }
+        // (wave-uniform) the causal / window select runs only where the tile reaches past the wave's first query or in front of its last query's window
+        const bool edge = has_dead || kt0 + 63 > pw_first || (p.window > 0 && kt0 < pw_last - p.window + 1);
+        bf16x8 pf[2][2];
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+            float* sq = s[qb];
+            if (edge) {                           // (a dead key's score may be NaN here -- NaN codes, a NaN scale: it is selected away, like the masked ones)
+                const int lo = p.window > 0 ? max(qpos[qb] - p.window + 1, lo_min) : lo_min;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) sq[j] = (kb + j > qpos[qb] || kb + j < lo) ? -INFINITY : sq[j];
+            }
+            float mx = sq[0];
+#pragma unroll
+            for (int j = 1; j < 16; ++j) mx = fmaxf(mx, sq[j]);
+            mx = xor32_max(xor16_max(mx));
+            const float m_new = fmaxf(m_run[qb], mx);
+            const float mc = (m_new == -INFINITY ? 0.f : m_new) * p.c;              // a row that has seen no key yet keeps m = -inf: guard the subtraction
+            const bool moved = m_new != m_run[qb];
+            const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run[qb], p.c, -mc));
+            m_run[qb] = m_new;
+            float psum = 0.f;
+#pragma unroll
+            for (int hk = 0; hk < 2; ++hk) {      // keys kb + 8 hk .. + 7: one PV operand; their V scales come from the strip for each of the two queries
+                float pe[8];
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    f32x4 vv = *(const f32x4*)(Sl + 256 + (g * 16 + hk * 8 + a * 4) * 4);
+                    if (has_dead) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const int key = kb + hk * 8 + a * 4 + r; vv[r] = (key >= nk || key < lo_min) ? 0.f : vv[r]; }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r += 2) {
+                        const int j = hk * 8 + a * 4 + r;
+                        const float e0 = __builtin_amdgcn_exp2f(fmaf(sq[j], p.c, -mc)), e1 = __builtin_amdgcn_exp2f(fmaf(sq[j + 1], p.c, -mc));
+                        const uint32_t er = pack2bf(e0, e1);                         // the row sum adds the rounded, unscaled e
+                        psum += __uint_as_float(er << 16) + __uint_as_float(er & 0xffff0000u);
+                        pe[a * 4 + r] = e0 * vv[r];                                  // the V scale rides in P, folded in before the one rounding to bf16
+                        pe[a * 4 + r + 1] = e1 * vv[r + 1];
+                    }
+                }
+                pf[qb][hk] = make8<false>(pe);
+            }
+            if (__builtin_amdgcn_ballot_w64(moved) != 0) {
+#pragma unroll
+                for (int df = 0; df < 8; ++df) o[qb][df] *= alpha;
+                l_run[qb] *= alpha;
+            }
+            l_run[qb] += psum;
+            __builtin_amdgcn_sched_barrier(0);    // (one query block's softmax at a time: interleaved, the two spill)
+        }
+        // ---- O^T += V^T . P'^T: bytes 0..7 / 8..15 of a V fragment against P' of the lane's keys 0..7 / 8..15
+#pragma unroll
+        for (int df = 0; df < 8; ++df) {
+            const bf16x8 v0 = kv8_to_bf16(vq[df][0], vq[df][1]), v1 = kv8_to_bf16(vq[df][2], vq[df][3]);
+            o[0][df] = mfma16<false>(v0, pf[0][0], o[0][df]);
+            o[1][df] = mfma16<false>(v0, pf[1][0], o[1][df]);
+            o[0][df] = mfma16<false>(v1, pf[0][1], o[0][df]);
+            o[1][df] = mfma16<false>(v1, pf[1][1], o[1][df]);
+        }
+    }
+    // ---- store: lane (i, g) holds d = df*16 + g*4 + 0..3 of its two queries; the row sum is still split over the four g's.  (The output rows are worked out again
+    // from a lane id the compiler cannot trace back: as common subexpressions of the prologue they would sit in registers through the whole loop)
+    int lane2 = lane;
+    asm volatile("" : "+v"(lane2));
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const float l = xor32_sum(xor16_sum(l_run[qb]));
+        const int row = wave * 32 + qb * 16 + (lane2 & 15), qi = tq0 + (row >> gs);
+        if (qi >= n) continue;
+        const size_t orow = (size_t)(row0 + qi) * p.H + (kvh << gs) + (row & ((1 << gs) - 1));
+        if (p.splits == 1) {
+            const float inv = 1.0f / l;
+            bf16_t* dst = p.ctx + orow * DH + (lane2 >> 4) * 4;
+#pragma unroll
+            for (int df = 0; df < 8; ++df) {
+                const f32x4 v = o[qb][df] * inv;
+                *(u32x2*)(dst + df * 16) = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+            }
+        } else {
+            const size_t prow = (size_t)z * p.rows * p.H + orow;
+            float* dst = p.part_o + prow * DH + (lane2 >> 4) * 4;
+#pragma unroll
+            for (int df = 0; df < 8; ++df) *(f32x4*)(dst + df * 16) = o[qb][df];
+            if (lane2 < 16) *(f32x2*)(p.part_ml + prow * 2) = f32x2{m_run[qb], l};
+        }
+    }
+}
+
+extern "C" int sm_llm_attention_ragged_fp8(const void* q, const void* const* kc_tab_dev, const void* const* vtc_tab_dev, const int32_t* seg_dev, const int32_t* work_dev,
+                                           int n_work, int rows, int H, int KV, int dh, int window, float* workspace, size_t workspace_floats, int splits, void* ctx,
+                                           void* stream) {
+    SM_REQUIRE(q && kc_tab_dev && vtc_tab_dev && seg_dev && work_dev && ctx && n_work > 0 && rows > 0 && window >= 0 && H > 0 && KV > 0, "sm_llm_attention_ragged_fp8: bad args");
+    SM_REQUIRE(dh == 128, "sm_llm_attention_ragged_fp8: the fp8 K / V cache takes head_dim 128 only (got %d)", dh);
+    SM_REQUIRE(H % KV == 0, "sm_llm_attention_ragged_fp8: H %% KV (H = %d, KV = %d)", H, KV);
+    const int G = H / KV;
+    SM_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "sm_llm_attention_ragged_fp8: H / KV = %d (1, 2, 4 or 8 query heads per K / V head)", G);
+    SM_REQUIRE(splits >= 1 && splits <= 64, "sm_llm_attention_ragged_fp8: 1 <= splits <= 64 (got %d)", splits);
+    const size_t prow = (size_t)rows * H;
+    SM_REQUIRE(splits == 1 || (workspace && workspace_floats >= (size_t)splits * prow * (dh + 2)), "sm_llm_attention_ragged_fp8: %d splits of %zu rows do not fit a workspace of %zu floats", splits, prow, workspace_floats);
+    SM_REQUIRE((((uintptr_t)q | (uintptr_t)ctx | (uintptr_t)workspace) & 15) == 0, "sm_llm_attention_ragged_fp8: q, ctx and the workspace must be 16-byte aligned");
+    SM_REQUIRE((long)n_work * KV * splits < (1L << 31), "sm_llm_attention_ragged_fp8: grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    RaggedP p;
+    p.q = (const bf16_t*)q; p.ctx = (bf16_t*)ctx; p.kc = kc_tab_dev; p.vtc = vtc_tab_dev; p.seg = seg_dev; p.work = work_dev;
+    p.rows = rows; p.H = H; p.KV = KV; p.window = window; p.splits = splits;
+    p.g_shift = G == 1 ? 0 : G == 2 ? 1 : G == 4 ? 2 : 3;
+    p.part_o = workspace; p.part_ml = splits > 1 ? workspace + (size_t)splits * prow * dh : nullptr;
+    p.c = (1.0f / sqrtf((float)dh)) * 1.4426950408889634f;
+    {
+        SmProfScope prof(SM_PROF_ATTN, st);
+        const dim3 grid((unsigned)(n_work * KV * splits));
+        ragged_attn_fp8_kernel<<<grid, 256, 0, st>>>(p);
+        SM_LAUNCH_CHECK();
+    }
+    if (splits > 1) {
+        // (rows of the matrix that belong to no stream have no partials: the merge leaves unspecified values in their context rows, as the kernel leaves them unwritten)
+        attn_combine_kernel<<<dim3((unsigned)prow, 1), 64, 0, st>>>(p.part_o, p.part_ml, splits, (int)prow, dh, p.c, p.ctx, 0, 0, 0);
+        SM_LAUNCH_CHECK();
+    }
+    return SM_OK;
+}

@@ -97,12 +97,12 @@ __global__ __launch_bounds__(64) void rope_kv_fp8_seg_kernel(const float* __rest
 // rotates 16 (d, d + 64) pairs with 16-byte loads; a K head's amax meets over the token's four lanes (two xor-shuffles) and each lane stores its 2 x 16 codes as
 // two 16-byte stores.  v heads: a lane holds 32 dims of its token, the amax is taken over the four lanes BEFORE the transpose, the codes cross a [128][64] byte
 // tile in LDS and leave as 64 consecutive positions of one dim per wave-store.  Same arithmetic as the row form above: identical bytes.
-__global__ __launch_bounds__(256) void rope_kv_fp8_tile_kernel(const float* __restrict__ qkv, int n, int pos0, int H, int KV, const float* __restrict__ cos_tab,
-                                                               const float* __restrict__ sin_tab, bf16_t* __restrict__ q, uint8_t* __restrict__ kc,
-                                                               uint8_t* __restrict__ vtc, int S_max) {
+// (the body, shared with the ragged form below: rows t0 .. t0 + 63 of a run of n rows that starts at qkv / q and sits at positions pos0 ..)
+__device__ __forceinline__ void rope_kv_fp8_tile(const float* __restrict__ qkv, int n, int pos0, int t0, int hd, int H, int KV, const float* __restrict__ cos_tab,
+                                                 const float* __restrict__ sin_tab, bf16_t* __restrict__ q, uint8_t* __restrict__ kc, uint8_t* __restrict__ vtc,
+                                                 int S_max, uint8_t (&tile)[128][64 + 4]) {
     constexpr int DH = 128, HALF = 64;
-    __shared__ uint8_t tile[DH][64 + 4];
-    const int t0 = blockIdx.x * 64, hd = blockIdx.y, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int tl = tid >> 2, part = tid & 3;
     const bool live = t0 + tl < n;
     const int t = live ? t0 + tl : n - 1;              // a dead lane redoes the last row (the shuffles below need all four lanes of a token) and stores nothing
@@ -186,6 +186,25 @@ __global__ __launch_bounds__(256) void rope_kv_fp8_tile_kernel(const float* __re
         for (int e = 0; e < 32; ++e) dstv[(size_t)e * S_max] = tile[w * 32 + e][lane];
     }
 }
+__global__ __launch_bounds__(256) void rope_kv_fp8_tile_kernel(const float* __restrict__ qkv, int n, int pos0, int H, int KV, const float* __restrict__ cos_tab,
+                                                               const float* __restrict__ sin_tab, bf16_t* __restrict__ q, uint8_t* __restrict__ kc,
+                                                               uint8_t* __restrict__ vtc, int S_max) {
+    __shared__ uint8_t tile[128][64 + 4];
+    rope_kv_fp8_tile(qkv, n, pos0, blockIdx.x * 64, blockIdx.y, H, KV, cos_tab, sin_tab, q, kc, vtc, S_max, tile);
+}
+// ---- the rows of S streams in one matrix (sm_group_llm_prefill): seg [S][4] = (row0, n, pos0, cap) per stream, tiles [n_tiles][2] = (stream, first row of a
+// 64-row tile of that stream's rows) -- the tables of sm_rope_kv_append_ragged.  One block per (tile, head slot) runs the tile body above on its stream's run of
+// rows, at the stream's positions, into the stream's buffers with the stream's cap (V^T pitch, start of the scales): the bytes of sm_rope_kv_append_fp8 per
+// stream, also for streams of fewer than 32 rows (where that call takes the row kernel: identical bytes).  Nothing outside [pos0, pos0 + n) is written.
+__global__ __launch_bounds__(256) void rope_kv_fp8_ragged_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ seg, const int32_t* __restrict__ tiles,
+                                                                 int H, int KV, const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                                 bf16_t* __restrict__ q, void* const* __restrict__ kc_tab, void* const* __restrict__ vtc_tab) {
+    __shared__ uint8_t tile[128][64 + 4];
+    const int sidx = tiles[2 * blockIdx.x], t0 = tiles[2 * blockIdx.x + 1];
+    const int row0 = seg[4 * sidx], n = seg[4 * sidx + 1], pos0 = seg[4 * sidx + 2], cap = seg[4 * sidx + 3];
+    rope_kv_fp8_tile(qkv + (size_t)row0 * (H + 2 * KV) * 128, n, pos0, t0, blockIdx.y, H, KV, cos_tab, sin_tab, q + (size_t)row0 * H * 128, (uint8_t*)kc_tab[sidx],
+                     (uint8_t*)vtc_tab[sidx], cap, tile);
+}
 
 static int kv8_check(const char* who, int dh, int KV, int H, int S_max) {
     SM_REQUIRE(dh == 128, "%s: the fp8 K / V cache takes head_dim 128 only (got %d)", who, dh);
@@ -203,6 +222,14 @@ extern "C" int sm_rope_kv_append_fp8(const float* qkv, int n, int pos0, int H, i
                                                                                                 (uint8_t*)vtcache, S_max);
     else
         rope_kv_fp8_kernel<<<dim3(n, H + 2 * KV), 64, 0, (hipStream_t)stream>>>(qkv, pos0, H, KV, cos_tab, sin_tab, (bf16_t*)q, (uint8_t*)kcache, (uint8_t*)vtcache, S_max);
+    SM_LAUNCH_CHECK();
+    return SM_OK;
+}
+extern "C" int sm_rope_kv_append_fp8_ragged(const float* qkv, const int32_t* seg_dev, const int32_t* tiles_dev, int n_tiles, int H, int KV, const float* cos_tab,
+                                            const float* sin_tab, void* q, void* const* kc_tab_dev, void* const* vtc_tab_dev, void* stream) {
+    SM_REQUIRE(qkv && seg_dev && tiles_dev && cos_tab && sin_tab && q && kc_tab_dev && vtc_tab_dev && n_tiles > 0 && H > 0 && KV > 0 && H % KV == 0, "sm_rope_kv_append_fp8_ragged: bad args");
+    SM_REQUIRE((((uintptr_t)qkv | (uintptr_t)q | (uintptr_t)cos_tab | (uintptr_t)sin_tab) & 15) == 0, "sm_rope_kv_append_fp8_ragged: qkv, q and the RoPE tables must be 16-byte aligned");
+    rope_kv_fp8_ragged_kernel<<<dim3(n_tiles, H + 2 * KV), 256, 0, (hipStream_t)stream>>>(qkv, seg_dev, tiles_dev, H, KV, cos_tab, sin_tab, (bf16_t*)q, kc_tab_dev, vtc_tab_dev);
     SM_LAUNCH_CHECK();
     return SM_OK;
 }

@@ -1924,6 +1924,8 @@ extern "C" int sm_group_llm_decode(sm_stream_group* g, const int32_t* active_hos
 // What is per stream by nature -- embedding + splice, RoPE + append, causal attention against the stream's own cache, the last row's head -- runs as ONE launch
 // over a device-side table that is uploaded once per call: per participating stream the K / V^T pointers of every layer, its token store, and per pass its
 // (row0, n, pos0, cap), the attention's sorted work list and the append's row tiles.  Capacities are not equalised: every stream keeps its own pitch.
+// kv_fp8 + kv_fp8_chunk models run the same pass over the same table with the FP8 pair (sm_rope_kv_append_fp8_ragged, sm_llm_attention_ragged_fp8): the table's
+// pointers are then the streams' code + scale buffers and cap also places the scales.  kv_fp8 alone stays stream by stream (bit-equal to solo prefill).
 // the last row of every stream that ends in this pass -> its row of the head's input
 __global__ void gather_last_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ seg, const int32_t* __restrict__ fin, int D, float* __restrict__ out) {
     const int s = blockIdx.x, dst = fin[s];
@@ -1954,8 +1956,10 @@ extern "C" int sm_group_llm_prefill(sm_stream_group* g, const int32_t* ids_dev, 
     SM_REQUIRE(P <= SM_GROUP_DECODE_MAX, "sm_group_llm_prefill: %d participating streams exceed %d", P, SM_GROUP_DECODE_MAX);
     const int ld = c.llm_hidden, H = c.llm_heads, KV = c.llm_kv_heads, dh = ld / H, qn = H * dh, kn = KV * dh, V = c.llm_vocab, G = H / KV;
     int rc;
-    // the fp8 cache (its ragged append and attention do not exist yet), other head shapes, and a lone stream (its own loop, today's numerics): stream by stream
-    if (m->kv_fp8 || dh != 128 || H % KV != 0 || !(G == 1 || G == 2 || G == 4 || G == 8) || P == 1) {
+    // the fp8 cache without kv_fp8_chunk (multi-row calls read a bf16 expansion there: no ragged form), other head shapes, and a lone stream (its own loop,
+    // today's numerics): stream by stream.  kv_fp8 + kv_fp8_chunk takes the batched pass with the FP8 pair of ragged launches
+    const bool fp8 = m->kv_fp8;
+    if ((fp8 && !m->kv_fp8_chunk) || dh != 128 || H % KV != 0 || !(G == 1 || G == 2 || G == 4 || G == 8) || P == 1) {
         size_t off = 0;
         for (int t = 0; t < P; ++t) { if ((rc = sm_llm_prefill(act[t], ids_dev + off, cnt[t], stream))) return rc; off += cnt[t]; }
         return SM_OK;
@@ -2036,10 +2040,17 @@ extern "C" int sm_group_llm_prefill(sm_stream_group* g, const int32_t* ids_dev, 
             {   sm_linear_t a = lin(m, *w.qkv, W->xnb.p, SM_X_BF16, n, ld);
                 a.out_f32 = W->qkvf.as<float>(); a.ldo = qn + 2 * kn;
                 if ((rc = sm_linear(&a, stream))) return rc; }
-            if ((rc = sm_rope_kv_append_ragged(W->qkvf.as<float>(), seg, (const int32_t*)(tb + ps.tiles), ps.n_tiles, H, KV, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p,
-                                               tab_kc + (size_t)l * P + ps.a, tab_vtc + (size_t)l * P + ps.a, f16, stream))) return rc;
-            if ((rc = sm_llm_attention_ragged(W->qb.p, (const void* const*)(tab_kc + (size_t)l * P + ps.a), (const void* const*)(tab_vtc + (size_t)l * P + ps.a), seg,
-                                              (const int32_t*)(tb + ps.work), ps.n_work, n, H, KV, dh, c.llm_sliding_window, f16, g->p_ws.as<float>(), ws_floats, ps.splits, W->ctxb.p, stream))) return rc;
+            if (fp8) {
+                if ((rc = sm_rope_kv_append_fp8_ragged(W->qkvf.as<float>(), seg, (const int32_t*)(tb + ps.tiles), ps.n_tiles, H, KV, m->rope_cos.as<float>(), m->rope_sin.as<float>(),
+                                                       W->qb.p, tab_kc + (size_t)l * P + ps.a, tab_vtc + (size_t)l * P + ps.a, stream))) return rc;
+                if ((rc = sm_llm_attention_ragged_fp8(W->qb.p, (const void* const*)(tab_kc + (size_t)l * P + ps.a), (const void* const*)(tab_vtc + (size_t)l * P + ps.a), seg,
+                                                      (const int32_t*)(tb + ps.work), ps.n_work, n, H, KV, dh, c.llm_sliding_window, g->p_ws.as<float>(), ws_floats, ps.splits, W->ctxb.p, stream))) return rc;
+            } else {
+                if ((rc = sm_rope_kv_append_ragged(W->qkvf.as<float>(), seg, (const int32_t*)(tb + ps.tiles), ps.n_tiles, H, KV, m->rope_cos.as<float>(), m->rope_sin.as<float>(), W->qb.p,
+                                                   tab_kc + (size_t)l * P + ps.a, tab_vtc + (size_t)l * P + ps.a, f16, stream))) return rc;
+                if ((rc = sm_llm_attention_ragged(W->qb.p, (const void* const*)(tab_kc + (size_t)l * P + ps.a), (const void* const*)(tab_vtc + (size_t)l * P + ps.a), seg,
+                                                  (const int32_t*)(tb + ps.work), ps.n_work, n, H, KV, dh, c.llm_sliding_window, f16, g->p_ws.as<float>(), ws_floats, ps.splits, W->ctxb.p, stream))) return rc;
+            }
             {   sm_linear_t a = lin(m, *w.o, W->ctxb.p, SM_X_BF16, n, qn);
                 a.residual = x; a.ldr = ld; a.out_f32 = x; a.ldo = ld;
                 a.post_ln_gamma = w.ln2_w; a.post_ln_eps = c.llm_eps; a.post_ln_out = W->xnb.p; a.post_ln_ldo = ld;

@@ -398,7 +398,8 @@ class NativeStreamGroup:
 
     def prefill(self, ids_per_stream: Sequence[Optional[torch.Tensor]]) -> None:
         """batched ragged prefill (sm_group_llm_prefill): one entry per stream of the group, int32 [n_i] on the GPU (conventions of NativeStream.prefill) or None /
-        empty for a stream that takes no part; per stream the result of its own prefill, with one pass over the LLM weights for all of them"""
+        empty for a stream that takes no part; per stream the result of its own prefill, with one pass over the LLM weights for all of them (16-bit caches, and
+        the FP8 cache with kv_fp8_chunk; kv_fp8 alone runs one prefill per stream)"""
         S = len(self.streams)
         assert len(ids_per_stream) == S, "one entry (ids or None) per stream of the group"
         parts = [t for t in ids_per_stream if t is not None and t.numel() > 0]

@@ -302,7 +302,8 @@ class MultiStreamSession:
         (NativeStream.set_sampling) and still decode through the batched call, next to the greedy streams of the group.
         batched_prefill=True: the streams that fire in one tick prefill their grown prompts TOGETHER (NativeStreamGroup.prefill, sm_group_llm_prefill: one pass
         over the LLM weights and one ragged attention launch per layer for all of them) instead of one prefill each; same events, the reply ids are the ids of
-        the same logits up to fp32 summation order.  A fire that waited behind a running reply (continuous mode) still starts with its own prefill."""
+        the same logits up to fp32 summation order.  Models with the FP8 K / V cache batch too when kv_fp8_chunk is on (ragged append + attention over the
+        codes); kv_fp8 alone prefills the firing streams one by one inside that call.  A fire that waited behind a running reply (continuous mode) still starts with its own prefill."""
         assert len(models) >= 1 and all(m.native is models[0].native for m in models), "the streams must share one NativeModel"
         self.models, self.tok = list(models), tokenizer
         self.native = models[0].native

@@ -4,8 +4,11 @@ attention of the 16-bit cache -- Mistral-7B widths, bf16, ONE process, the legs 
                      `serial` = the S streams prefilled one by one, `group` = one group prefill; every call starts from kv_len 2048 again
   chunk_attn_us      HIP-event time of one layer's attention for (n, pos0) = (16, 4080) and (64, 4032), H = 32, KV = 8, capacity 4096: `prefill` = sm_llm_attention,
                      `ragged` = sm_llm_attention_ragged with S = 1 incl. its split merge (the plan is made once, outside the bracket); 200 calls per bracket
+With `fp8` the model holds the FP8 K / V cache with kv_fp8_chunk (the batched pass runs sm_rope_kv_append_fp8_ragged + sm_llm_attention_ragged_fp8; `serial` is
+what the group call did for this model before that pass existed) and chunk_attn_us times `fused` = sm_llm_attention_fp8 against `ragged` =
+sm_llm_attention_ragged_fp8.
 
-    python tools/group_prefill_bench.py [rounds]"""
+    python tools/group_prefill_bench.py [rounds] [fp8]"""
 import ctypes as C
 import json, os, statistics, sys, time
 import torch
@@ -13,10 +16,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.kv_fp8_bench import make_model
 
 
-def chunk_attn_us(lib, rounds):
+def chunk_attn_us(lib, rounds, fp8=False):
     H, KV, cap = 32, 8, 4096
     g = torch.Generator(device="cuda").manual_seed(3)
-    kb, vb = (torch.randn(cap * KV * 128, device="cuda", generator=g).bfloat16() for _ in range(2))
+    if fp8:                                                   # finite codes, scales 2^-6 (tools/kv_fp8_bench.py's cache)
+        kb, vb = (torch.randint(0, 0x78, (cap * KV * 132,), dtype=torch.uint8, device="cuda", generator=g) for _ in range(2))
+        for b in (kb, vb):
+            b[cap * KV * 128:].view(torch.float32).fill_(2.0 ** -6)
+    else:
+        kb, vb = (torch.randn(cap * KV * 128, device="cuda", generator=g).bfloat16() for _ in range(2))
     q = torch.randn(64, H * 128, device="cuda", generator=g).bfloat16()
     ctx, ws = torch.empty_like(q), torch.empty(2048 * H * 130, device="cuda")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -30,6 +38,9 @@ def chunk_attn_us(lib, rounds):
         seg_d, work_d = seg.cuda(), work.cuda()
         legs = {"prefill": lambda: lib.sm_llm_attention(P(q), P(kb), P(vb), n, pos0, H, KV, 128, cap, P(ctx), st),
                 "ragged": lambda: lib.sm_llm_attention_ragged(P(q), P(kt), P(vt), P(seg_d), P(work_d), nw.value, n, H, KV, 128, 0, 0, P(ws), ws.numel(), sp.value, P(ctx), st)}
+        if fp8:
+            legs = {"fused": lambda: lib.sm_llm_attention_fp8(P(q), P(kb), P(vb), n, pos0, H, KV, 128, cap, 0, P(ws), ws.numel(), P(ctx), st),
+                    "ragged": lambda: lib.sm_llm_attention_ragged_fp8(P(q), P(kt), P(vt), P(seg_d), P(work_d), nw.value, n, H, KV, 128, 0, P(ws), ws.numel(), sp.value, P(ctx), st)}
         per = {name: [] for name in legs}
         for _ in range(rounds):
             for name, fn in legs.items():
@@ -44,11 +55,11 @@ def chunk_attn_us(lib, rounds):
     return out
 
 
-def main(rounds=3):
-    cfg, m = make_model()
+def main(rounds=3, fp8=False):
+    cfg, m = make_model(kv_fp8=True, kv_fp8_chunk=True) if fp8 else make_model()
     g = torch.Generator(device="cuda").manual_seed(17)
     ids = lambda n: torch.randint(3, 32000, (n,), generator=g, device="cuda", dtype=torch.int32)
-    res = {"group_prefill_ms": {}, "chunk_attn_us": chunk_attn_us(m.lib, rounds)}
+    res = {"group_prefill_ms": {}, "chunk_attn_us": chunk_attn_us(m.lib, rounds, fp8)}
     streams = [m.open_stream(max_frames=8, max_seq=2304) for _ in range(32)]
     ctx = ids(2048)
     for s in streams:
@@ -80,4 +91,5 @@ def main(rounds=3):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 3)
+    args = [a for a in sys.argv[1:] if a != "fp8"]
+    main(int(args[0]) if args else 3, "fp8" in sys.argv[1:])
